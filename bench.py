@@ -17,6 +17,13 @@ Default workload: BASELINE config 2 -- the sf_e_110-shape instance
 pool is withheld) at 10^6 panels per GPU per step (weak scaling), 400 timed
 steps (~2 s).  Rank 0 prints ONE JSON line.  The instance and every buffer are
 resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the steps and prints the headline (metric, value, unit,
+ms_per_step, dtype, the workload).  --full adds everything else the benchmark measures or checks,
+after the timed region: the digests and draw statistics of the last step, the per-kernel times
+(HIP events inside the timed region and a serial pass of each kernel alone), the roofline, the
+legacy_probabilities end-to-end leg, the CPU baselines and (N > 1) the one-process multi-device
+comparison.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import glob
@@ -58,6 +65,13 @@ def parse():
     ap.add_argument("--panels", type=int, default=0, help="panels per GPU per step (0 = config default)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-pairs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run and report everything beside the headline: result "
+                         "digests and draw statistics, per-kernel times and the roofline, the API leg, the CPU "
+                         "baselines, (N > 1) the one-process multi-device comparison")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the results of the last timed step (per-person counts, pair counts, distinct "
+                         "count, a fixed sample of the drawn panels) as DIR/<name>.npy")
     ap.add_argument("--pair-engine", default="fp4", choices=sorted(PAIR_ENGINES))
     ap.add_argument("--no-overlap", action="store_true",
                     help="serialise every stage on one stream (default: draws on their own stream, "
@@ -78,12 +92,13 @@ def parse():
                          "matrix's diagonal) where the instance's draw kernel has one, else -- or with "
                          "'count' -- xt_count_kernel on the counting stream")
     ap.add_argument("--iso-steps", type=int, default=2,
-                    help="serial steps after the timed region that measure each kernel alone (not in `value`)")
+                    help="--full: serial steps after the timed region that measure each kernel alone (not in "
+                         "`value`)")
     ap.add_argument("--exchange", default="keys", choices=("keys", "bitmask"),
                     help="N > 1: distinct panels travel as 24-byte keys (default) or with their bitmasks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-baseline legs")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target duration of each CPU-baseline leg")
-    ap.add_argument("--no-api", action="store_true", help="skip the legacy_probabilities end-to-end leg")
+    ap.add_argument("--no-api", action="store_true", help="--full without the legacy_probabilities end-to-end leg")
     ap.add_argument("--job-panels", type=int, default=0,
                     help="strong scaling (BASELINE configs 3 and 5): time ONE job of this many panels split "
                          "over the N ranks (each rank's share in chunks of --panels; counts and pairs "
@@ -102,6 +117,43 @@ def digests(counts, pairs, n):
         m = pairs.view(n, n).cpu().numpy()
         out["pairs_triu_sha256"] = hashlib.sha256(np.ascontiguousarray(np.triu(m), "<i8").tobytes()).hexdigest()
     return out
+
+
+DUMP_PAIR_ENTRIES = 4 * 10 ** 6     # float64 pair counts written at most (32 MB)
+DUMP_PANEL_BITS = 4 * 10 ** 6       # float32 membership bits of the sampled panels written at most (16 MB)
+
+
+def dump_outputs(path, n, W, S, counts, pairs, unique, panels):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as <path>/<name>.npy
+    (under 64 MB in all).  counts: the n per-person counts; unique: the exact distinct-panel count;
+    pairs: the upper triangle (incl. the diagonal) of the n x n pair counts, whole (zeros below the
+    diagonal) while it has at most DUMP_PAIR_ENTRIES entries, else half as many entries (i <= j) at seeded
+    positions, the positions in pairs_index.npy; panels: the membership bits (one row of 64 W zeros and
+    ones per panel) of a seeded sample of the S drawn panels, the rows in panels_index.npy.  The samples
+    depend on the shape only, so two runs with the same arguments write the same entries."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+    rng = np.random.default_rng(0)
+    save("counts", counts.cpu().numpy().astype(np.float64))
+    save("unique", np.array([int(unique.item())], np.float64))
+    if pairs is not None:
+        if n * n <= DUMP_PAIR_ENTRIES:
+            save("pairs", np.triu(pairs.view(n, n).cpu().numpy()).astype(np.float64))
+        else:
+            i, j = rng.integers(0, n, size=(2, DUMP_PAIR_ENTRIES // 2))   # half: their positions are written too
+            idx = np.sort(np.minimum(i, j) * n + np.maximum(i, j))
+            save("pairs_index", idx.astype(np.float64))
+            save("pairs", pairs[torch.from_numpy(idx).to(pairs.device)].cpu().numpy().astype(np.float64))
+    rows = np.sort(rng.integers(0, S, size=max(1, min(S, DUMP_PANEL_BITS // (64 * W)))))
+    words = panels[: S * W].view(S, W)[torch.from_numpy(rows).to(panels.device)].cpu().numpy().view(np.uint64)
+    bits = (words[:, :, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)
+    save("panels_index", rows.astype(np.float64))
+    save("panels", bits.reshape(len(rows), 64 * W).astype(np.float32))
 
 
 def cpu_model():
@@ -423,15 +475,21 @@ def run_job(args, world, rank, dev, torch, dist, A, Dd, enc, k, S, inst_dir, pip
         st = torch.tensor([steps], dtype=torch.int64, device=dev)
         dist.all_reduce(st, op=dist.ReduceOp.MAX)
         steps = int(st.item())
-    checks = {"job_unique": int(u.item()), "job_count_sum": int(pipe.counts.sum().item()),
-              "job_pair_sum": int(torch.triu(pipe.pairs.view(enc.n, enc.n)).sum().item()) if want_pairs else None}
-    checks.update({"job_" + key: v for key, v in digests(pipe.counts, pipe.pairs if want_pairs else None,
-                                                       enc.n).items()})
-    stt = torch.tensor(list(A.draw_stats(enc).values()), dtype=torch.int64, device=dev)
-    if world > 1:
-        Dd._all_reduce(stt)
-    draw_stats = dict(zip(A.STAT_KEYS, (int(x) for x in stt.cpu().tolist())))
-    draw_stats["panels"] = Pj
+    if args.dump_outputs and rank == 0:
+        # rank 0's share of the panels; counts, pairs and the distinct count are the whole job's
+        dump_outputs(args.dump_outputs, enc.n, W, max(share, 1), pipe.counts, pipe.pairs if want_pairs else None,
+                     u, panels_all)
+    checks = draw_stats = None
+    if args.full:
+        checks = {"job_unique": int(u.item()), "job_count_sum": int(pipe.counts.sum().item()),
+                  "job_pair_sum": int(torch.triu(pipe.pairs.view(enc.n, enc.n)).sum().item()) if want_pairs else None}
+        checks.update({"job_" + key: v for key, v in digests(pipe.counts, pipe.pairs if want_pairs else None,
+                                                           enc.n).items()})
+        stt = torch.tensor(list(A.draw_stats(enc).values()), dtype=torch.int64, device=dev)
+        if world > 1:
+            Dd._all_reduce(stt)
+        draw_stats = dict(zip(A.STAT_KEYS, (int(x) for x in stt.cpu().tolist())))
+        draw_stats["panels"] = Pj
     result = {
         "metric": "LEGACY panels/sec (node) at sf_e_110 shape; XtX MFMA util; speedup vs CPU",
         "value": Pj / elapsed,
@@ -454,10 +512,9 @@ def run_job(args, world, rank, dev, torch, dist, A, Dd, enc, k, S, inst_dir, pip
                    "pipeline": ("chunk draws on the draw stream, each writing its XT operand (3-buffer ring); the "
                                 "pair kernel follows per chunk, the counts are the pair diagonal") if xt_draw else
                                "every chunk's draw enqueued at once on the draw stream; counting follows per chunk"},
-        "checks": checks,
-        "draw_stats": draw_stats,
-        "cpu_baseline": None,
     }
+    if args.full:
+        result.update({"checks": checks, "draw_stats": draw_stats, "cpu_baseline": None})
     if rank == 0:
         print(json.dumps(result))
     if world > 1:
@@ -640,7 +697,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     A.draw_stats(enc, reset=True)     # SelectionErrors / rejections of the timed draws only
-    log = {}
+    log = {} if args.full else None   # --full: HIP events around every stage of the timed steps
     t0 = time.perf_counter()
     run_steps(args.warmup, args.steps, log)
     torch.cuda.synchronize()
@@ -653,6 +710,40 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    n = enc.n
+    total = S * world * args.steps
+    result = {
+        "metric": "LEGACY panels/sec (node) at sf_e_110 shape; XtX MFMA util; speedup vs CPU",
+        "value": total / elapsed,
+        "unit": "panels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32/u64 (integer draw), %s MFMA -> exact int pairs" % args.pair_engine,
+        "data": "synthetic instance %s (tests/golden/instances), Philox seed %d" % (inst_dir, args.seed),
+        "config": {"workload": "%s: %d LEGACY panels/GPU/step, k=%d, n=%d, C=%d, F=%d, counts+%sunique" % (
+            args.config, S, k, n, enc.C, enc.F, "pairs+" if want_pairs else ""),
+            "panels_per_gpu_per_step": S, "instance": inst_dir, "parallelism": "panel shards x%d" % world,
+            "pipeline": ("draws on their own stream, %d steps ahead of the counting%s" % (
+                ahead, " and the exchange" if world > 1 else "")) if overlap else "serial",
+            "xt_operand": ("written by the draw kernel's fused pack (one XT buffer per panel buffer); counts = "
+                           "the stored pair matrix's diagonal") if any(fused_xt) else "xt_count_kernel"},
+    }
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, read before any later step overwrites them (N > 1: rank 0's panels)
+        dump_outputs(args.dump_outputs, n, W, S, pipe.counts, pipe.pairs if want_pairs else None, last["unique"],
+                     pbufs[(args.warmup + args.steps - 1) % nb])
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # results of the last timed step (whole job): a rehearsal of --gpus N --panels P must match a
     # single-GPU run with --panels N*P (same global panel indices)
@@ -716,7 +807,6 @@ def main():
         torch.cuda.synchronize()
         pipe.check_status()
     stage_ms = stage_times(iso) if iso else stage_pipe
-    n = enc.n
     npad = pipe.npad
     nblk = (S + 63) // 64
     draw_bytes = S * 2 * k if split else S * (8 * W + 16)   # pick lists written (or bitmasks + hashes)
@@ -817,34 +907,14 @@ def main():
     roof["pmc_source_sha"] = sha
     roof["pmc_matches_sources"] = pmc_ok
 
-    total = S * world * args.steps
-    result = {
-        "metric": "LEGACY panels/sec (node) at sf_e_110 shape; XtX MFMA util; speedup vs CPU",
-        "value": total / elapsed,
-        "unit": "panels/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int32/u64 (integer draw), %s MFMA -> exact int pairs" % args.pair_engine,
-        "data": "synthetic instance %s (tests/golden/instances), Philox seed %d" % (inst_dir, args.seed),
-        "config": {"workload": "%s: %d LEGACY panels/GPU/step, k=%d, n=%d, C=%d, F=%d, counts+%sunique" % (
-            args.config, S, k, n, enc.C, enc.F, "pairs+" if want_pairs else ""),
-            "panels_per_gpu_per_step": S, "instance": inst_dir, "parallelism": "panel shards x%d" % world,
-            "pipeline": ("draws on their own stream, %d steps ahead of the counting%s" % (
-                ahead, " and the exchange" if world > 1 else "")) if overlap else "serial",
-            "xt_operand": ("written by the draw kernel's fused pack (one XT buffer per panel buffer); counts = "
-                           "the stored pair matrix's diagonal") if any(fused_xt) else "xt_count_kernel"},
+    result.update({
         "roofline": roof,
         "kernels": kernels,
         "kernel_timing": kernel_timing,
         "checks": checks,
         "draw_stats": draw_stats,
         "draw_stream_busy": draw_busy,
-    }
+    })
     if want_pairs:
         result["xtx_mfma_util"] = kernels["pairs_mfma"]["mfma_util"]
         result["xtx_int8_peak_equiv"] = kernels["pairs_mfma"]["int8_peak_equiv"]

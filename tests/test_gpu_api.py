@@ -246,7 +246,7 @@ def test_bench_self_launch_two_ranks_equals_one(gpu_available):
     own two ranks and prints one line with n_gpus 2 whose checks equal the N = 1 run over the same
     global panels; the one-process multi-device leg (csa_legacy_sample_devices over the ranks'
     devices) equals the rank-sharded result."""
-    common = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-api", "--iso-steps", "0"]
+    common = ["--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-api", "--iso-steps", "0"]
     two = _bench(["--gpus", "2", "--panels", "20000"] + common, {"CSA_BENCH_BACKEND": "gloo"})
     one = _bench(["--gpus", "1", "--panels", "40000"] + common, {})
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1
@@ -266,7 +266,7 @@ def test_bench_job_mode_two_ranks_equals_one(gpu_available, config, panels, chun
     counts / pairs, the exact distinct count over the whole job): the 2-rank gloo rehearsal on this GPU
     and the 1-GPU run agree on the count vector and the pair triangle (SHA-256 digests), the distinct
     count and the draw statistics; uneven shares (P odd) and a ragged last chunk included."""
-    common = ["--config", config, "--job-panels", str(panels), "--panels", str(chunk), "--warmup", "1",
+    common = ["--full", "--config", config, "--job-panels", str(panels), "--panels", str(chunk), "--warmup", "1",
               "--no-cpu-baseline", "--no-api"]
     two = _bench(["--gpus", "2"] + common, {"CSA_BENCH_BACKEND": "gloo"})
     one = _bench(["--gpus", "1"] + common, {})

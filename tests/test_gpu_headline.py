@@ -213,8 +213,8 @@ def test_bench_job_xt_from_draw_equals_transpose(gpu_available, config, job, chu
     from conftest import REPO
     out = {}
     for mode in ("draw", "count"):
-        r = subprocess.run([sys.executable, "bench.py", "--config", config, "--job-panels", str(job), "--panels",
-                            str(chunk), "--warmup", "1", "--no-cpu-baseline", "--no-api", "--xt-from", mode],
+        r = subprocess.run([sys.executable, "bench.py", "--full", "--config", config, "--job-panels", str(job),
+                            "--panels", str(chunk), "--warmup", "1", "--no-cpu-baseline", "--no-api", "--xt-from", mode],
                            cwd=REPO, capture_output=True, text=True, timeout=240)
         assert r.returncode == 0, r.stderr[-2000:]
         out[mode] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -18,8 +18,8 @@ run() {  # label, command...
   done
   wait $pid; echo "[$label rc=$?]"
 }
-run step timeout -k 10 300 python bench.py --config synthetic8192 --steps 40 --warmup 2 --iso-steps 0 --no-cpu-baseline --no-api
-run draw_only timeout -k 10 300 python bench.py --config synthetic8192 --no-pairs --steps 60 --warmup 2 --iso-steps 0 --no-cpu-baseline --no-api
+run step timeout -k 10 300 python bench.py --full --config synthetic8192 --steps 40 --warmup 2 --iso-steps 0 --no-cpu-baseline --no-api
+run draw_only timeout -k 10 300 python bench.py --full --config synthetic8192 --no-pairs --steps 60 --warmup 2 --iso-steps 0 --no-cpu-baseline --no-api
 run pairs_only timeout -k 10 300 python tools/pair_bench.py --n 8192 --variants tile4 --reps 80
-run sf_e timeout -k 10 300 python bench.py --steps 1500 --warmup 2 --iso-steps 0 --no-cpu-baseline --no-api
+run sf_e timeout -k 10 300 python bench.py --full --steps 1500 --warmup 2 --iso-steps 0 --no-cpu-baseline --no-api
 echo done

@@ -19,7 +19,7 @@ for rep in $(seq 1 "${REPS:-2}"); do
   for ent in $ENTRIES; do
     label=${ent%%:*}; envs=""; [ "$label" != "$ent" ] && envs=${ent#*:}
     ( IFS=','; for kv in $envs; do export "$kv"; done
-      timeout -k 10 300 python bench.py --steps ${STEPS:-100} --warmup 3 --no-cpu-baseline --no-api "$@" \
+      timeout -k 10 300 python bench.py --full --steps ${STEPS:-100} --warmup 3 --no-cpu-baseline --no-api "$@" \
           > "$OUT/ab_$label.json" 2> "$OUT/ab_$label.err" )
     rc=$?; [ $rc -eq 0 ] || { echo "rc=$rc $ent"; tail -3 "$OUT/ab_$label.err"; exit $rc; }
     python3 -c "

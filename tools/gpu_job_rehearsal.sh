@@ -11,7 +11,7 @@ for spec in "example_large_200 $P3" "synthetic8192 $P5"; do
   set -- $spec; cfg=$1; P=$2
   for n in 1 2; do
     env_extra=""; [ $n -gt 1 ] && env_extra="CSA_BENCH_BACKEND=gloo"
-    env $env_extra timeout -k 10 500 python bench.py --config $cfg --job-panels $P --gpus $n --warmup 2 \
+    env $env_extra timeout -k 10 500 python bench.py --full --config $cfg --job-panels $P --gpus $n --warmup 2 \
         --no-cpu-baseline --no-api > "$OUT/job_${TAG}_${cfg}_n$n.json" 2> "$OUT/job_${TAG}_${cfg}_n$n.err"
     rc=$?; [ $rc -eq 0 ] || { echo "[$cfg n=$n] rc=$rc"; tail -5 "$OUT/job_${TAG}_${cfg}_n$n.err"; exit $rc; }
     python3 -c "

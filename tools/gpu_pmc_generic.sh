@@ -9,6 +9,6 @@ DEF="trace:--kernel-trace --stats|pmc_a:--pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MF
 IFS='|' read -ra PS <<< "${PASSES:-$DEF}"
 for pass in "${PS[@]}"; do
   name=${pass%%:*}; args=${pass#*:}
-  timeout -k 10 300 rocprofv3 $args -d "$OUT/$name" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
+  timeout -k 10 300 rocprofv3 $args -d "$OUT/$name" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
   rc=$?; echo "[$name] rc=$rc"; [ $rc -eq 0 ] || { tail -5 "$OUT/$name.err"; exit $rc; }
 done

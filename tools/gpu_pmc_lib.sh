@@ -10,7 +10,7 @@ for ent in $ENTRIES; do
   label=${ent%%:*}; lib=${ent#*:}
   if [ -n "$lib" ]; then export CSA_LIB=$ROOT/$lib; else unset CSA_LIB; fi
   timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE \
-      -d "$OUT/$label" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --iso-steps 0 --no-pairs \
+      -d "$OUT/$label" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --iso-steps 0 --no-pairs \
       --no-cpu-baseline --no-api "$@" > "$OUT/$label.json" 2> "$OUT/$label.err" || { echo "rc=$? $label"; tail -3 "$OUT/$label.err"; exit 1; }
   python3 - "$OUT/$label" "$label" <<'PY'
 import csv, glob, sys, collections

@@ -18,7 +18,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   fatal $rc && exit $rc
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
+  timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS:-} > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
   rc=$?; cut -c1-1500 "$OUT/bench_$TAG.json"; tail -3 "$OUT/bench_$TAG.err"; echo "[bench] rc=$rc"
   [ $rc -eq 0 ] || exit $rc
 fi
