@@ -1836,6 +1836,7 @@ struct DrawConfig {
     bool wide = false;  // draw_wide_kernel (8 lanes per panel)
     bool solo = false;  // draw_solo_kernel (1 lane per panel): FPL / WPL hold its FN / WN
     bool k8 = false;    // lane / solo: the 8-bit need keys carrying their index (csa_instance::need8)
+    int np = 8;         // lane / solo (FN >= 16): slack bit planes, csa_instance::max_slack < 2^np
     const void *fn = nullptr;
     bool picks() const { return lane || wide || solo; }  // pick-list kernels (picks_pack_kernel builds the panels)
 };
@@ -1865,48 +1866,75 @@ const void *wide_fn(int fpl, int wpl) {
 #ifndef CSA_LANE_SKDIV
 #define CSA_LANE_SKDIV 1
 #endif
-template <int FN, int WN, bool K8>
+template <int FN, int WN, int NP, bool K8>
 const void *lane_fn_wn() {
     constexpr int SK = (WN / 2 + CSA_LANE_SKDIV - 1) / CSA_LANE_SKDIV;
-    return reinterpret_cast<const void *>(&draw_lane_kernel<FN, WN, SK, K8>);
+    return reinterpret_cast<const void *>(&draw_lane_kernel<FN, WN, SK, NP, K8>);
 }
 
-template <int FN, bool K8>
+template <int FN, int NP, bool K8>
 const void *lane_fn_w(int wn) {
     switch (wn) {
-        case 4: return lane_fn_wn<FN, 4, K8>();
-        case 8: return lane_fn_wn<FN, 8, K8>();
-        case 16: return lane_fn_wn<FN, 16, K8>();
-        case 28: return lane_fn_wn<FN, 28, K8>();
-        case 32: return lane_fn_wn<FN, 32, K8>();
+        case 4: return lane_fn_wn<FN, 4, NP, K8>();
+        case 8: return lane_fn_wn<FN, 8, NP, K8>();
+        case 16: return lane_fn_wn<FN, 16, NP, K8>();
+        case 28: return lane_fn_wn<FN, 28, NP, K8>();
+        case 32: return lane_fn_wn<FN, 32, NP, K8>();
         default: return nullptr;
     }
 }
 
-template <int FN, bool K8>
+template <int FN, int NP, bool K8>
 const void *solo_fn_w(int wn) {
     switch (wn) {
-        case 4: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 4, K8>);
-        case 8: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 8, K8>);
-        case 16: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 16, K8>);
-        case 28: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 28, K8>);
-        case 32: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 32, K8>);
+        case 4: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 4, NP, K8>);
+        case 8: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 8, NP, K8>);
+        case 16: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 16, NP, K8>);
+        case 28: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 28, NP, K8>);
+        case 32: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 32, NP, K8>);
+        default: return nullptr;
+    }
+}
+
+// slack bit planes of the register kernels: the built plane counts, the smallest that holds max_slack
+int slack_planes(int max_slack) { return max_slack < 32 ? 5 : max_slack < 128 ? 7 : 8; }
+
+template <int FN, bool K8>
+const void *solo_fn_p(int wn, int np) {
+    if constexpr (FN < 16) {
+        return solo_fn_w<FN, 8, K8>(wn);  // no slack planes at FN = 8
+    } else {
+        switch (np) {
+            case 5: return solo_fn_w<FN, 5, K8>(wn);
+            case 7: return solo_fn_w<FN, 7, K8>(wn);
+            case 8: return solo_fn_w<FN, 8, K8>(wn);
+            default: return nullptr;
+        }
+    }
+}
+
+template <int FN, bool K8>
+const void *lane_fn_p(int wn, int np) {
+    switch (np) {
+        case 5: return lane_fn_w<FN, 5, K8>(wn);
+        case 7: return lane_fn_w<FN, 7, K8>(wn);
+        case 8: return lane_fn_w<FN, 8, K8>(wn);
         default: return nullptr;
     }
 }
 
 // k8: the 8-bit need keys with the feature index inside (csa_instance::need8; draw_lane.inc)
-const void *solo_fn(int fn_, int wn, bool k8) {
+const void *solo_fn(int fn_, int wn, bool k8, int np) {
     switch (fn_) {
-        case 8: return k8 ? solo_fn_w<8, true>(wn) : solo_fn_w<8, false>(wn);
-        case 16: return k8 ? solo_fn_w<16, true>(wn) : solo_fn_w<16, false>(wn);
+        case 8: return k8 ? solo_fn_p<8, true>(wn, np) : solo_fn_p<8, false>(wn, np);
+        case 16: return k8 ? solo_fn_p<16, true>(wn, np) : solo_fn_p<16, false>(wn, np);
         default: return nullptr;
     }
 }
 
-const void *lane_fn(int fn_, int wn, bool k8) {
+const void *lane_fn(int fn_, int wn, bool k8, int np) {
     switch (fn_) {
-        case 32: return k8 ? lane_fn_w<32, true>(wn) : lane_fn_w<32, false>(wn);
+        case 32: return k8 ? lane_fn_p<32, true>(wn, np) : lane_fn_p<32, false>(wn, np);
         default: return nullptr;
     }
 }
@@ -1976,7 +2004,8 @@ int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
         c.FPL = std::max(8, pow2_ceil_int(I->F));
         c.WPL = I->W <= 4 ? 4 : I->W <= 8 ? 8 : I->W <= 16 ? 16 : I->W <= 28 ? 28 : 32;
         c.k8 = I->need8;
-        c.fn = solo_fn(c.FPL, c.WPL, c.k8);
+        c.np = c.FPL >= 16 ? slack_planes(I->max_slack) : 8;
+        c.fn = solo_fn(c.FPL, c.WPL, c.k8, c.np);
         if (!c.fn) return fail(CSA_E_UNSUPPORTED, "no solo draw kernel for F=%d W=%d", I->F, I->W);
         return CSA_OK;
     }
@@ -1994,7 +2023,8 @@ int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
         c.FPL = std::max(8, pow2_ceil_int(I->F));
         c.WPL = I->W <= 4 ? 4 : I->W <= 8 ? 8 : I->W <= 16 ? 16 : I->W <= 28 ? 28 : 32;
         c.k8 = I->need8;
-        c.fn = lane_fn(c.FPL, c.WPL, c.k8);
+        c.np = slack_planes(I->max_slack);
+        c.fn = lane_fn(c.FPL, c.WPL, c.k8, c.np);
         if (!c.fn) return fail(CSA_E_UNSUPPORTED, "no lane draw kernel for F=%d W=%d", I->F, I->W);
         return CSA_OK;
     }
@@ -2768,10 +2798,10 @@ int csa_draw_kernel_name(const csa_instance *I, int32_t k, char *buf, uint64_t l
     rc = pick_draw_config(I, false, cfg);
     if (rc) return rc;
     if (cfg.solo)
-        snprintf(buf, (size_t)len, "draw_solo_kernel<%d, %d, %s>", cfg.FPL, cfg.WPL, cfg.k8 ? "true" : "false");
+        snprintf(buf, (size_t)len, "draw_solo_kernel<%d, %d, %d, %s>", cfg.FPL, cfg.WPL, cfg.np, cfg.k8 ? "true" : "false");
     else if (cfg.lane)
-        snprintf(buf, (size_t)len, "draw_lane_kernel<%d, %d, %d, %s>", cfg.FPL, cfg.WPL,
-                 (cfg.WPL / 2 + CSA_LANE_SKDIV - 1) / CSA_LANE_SKDIV, cfg.k8 ? "true" : "false");
+        snprintf(buf, (size_t)len, "draw_lane_kernel<%d, %d, %d, %d, %s>", cfg.FPL, cfg.WPL,
+                 (cfg.WPL / 2 + CSA_LANE_SKDIV - 1) / CSA_LANE_SKDIV, cfg.np, cfg.k8 ? "true" : "false");
     else if (cfg.wide)
         snprintf(buf, (size_t)len, "draw_wide_kernel<%d, %d, %d>", cfg.G, cfg.FPL, cfg.WPL);
     else

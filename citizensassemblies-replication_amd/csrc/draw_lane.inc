@@ -22,11 +22,13 @@
 //     never beats the sentinel, so the comparison against the sentinel start alone reproduces
 //     legacy.py:138-149.  The FAIL test `remaining < min - selected` is read off the maximum
 //     (ratio > 1, or need > 0 = remaining).
-//   * holder scan (legacy.py:186-197): the second lane keeps its words in REVERSED order (register j
-//     = word WN-1-j) and looks for the (remaining[f*] - r + 1)-th holder counted from the last
-//     agent, so each lane finds its candidate in ONE pass over its own words (no exchange of
-//     holder counts): it keeps the last word whose preceding holder count is < r, then
-//     select_bit inside it.
+//   * holder scan (legacy.py:186-197): the second lane keeps the pool MIRRORED -- its words in
+//     reversed order and each word bit-reversed (register j bit b = agent 64 WN - 1 - (64 j + b)) --
+//     and looks for the (remaining[f*] - r + 1)-th holder counted from the last agent, which in its
+//     own order is a plain scan from the start; so each lane finds its candidate in ONE pass over
+//     its own words (no exchange of holder counts): it keeps the last word whose preceding holder
+//     count is < r, then select_bit inside it, and the agent is off + sgn (64 word + bit) with
+//     per-lane constants (0, +1) / (64 WN - 1, -1).
 //   * delete_person (legacy.py:103-120): the picked person's feature mask (LDS) decrements need
 //     and remaining; "selected == max" is a zero test of bit-sliced max - selected planes.
 //   * delete_all_in_cat (legacy.py:47-62), bulk form: the cascading pairs of a step (up to
@@ -51,10 +53,10 @@ constexpr int kLaneSlots = 8;  // cascading pairs per cooperative round (~1.8 ca
 
 __host__ __device__ inline size_t lane_lds_bytes(int FN, int WN, int n) {
     const size_t LS = (size_t)WN + 1;
-    const size_t draw = (size_t)2 * FN * LS * 8 + 64                  // feature rows + reversed rows (+ skew)
+    const size_t draw = (size_t)2 * FN * LS * 8 + 64                  // feature rows + mirrored rows (+ skew)
                         + (size_t)((n + 3) & ~3) * 4                  // person feature masks
                         + (size_t)4 * FN * 4                          // need0, rem0, mnx, pad
-                        + (size_t)2 * WN * 8                          // attempt-start pool (+ reversed)
+                        + (size_t)2 * WN * 8                          // attempt-start pool (+ mirrored)
                         + (size_t)(kLaneThreads / 64) * kLaneSlots * WN * 8   // cascade slots
                         + (size_t)(kLaneThreads / 64) * kLaneSlots * FN * 4;  // cascade decrements
     // the fused pack reuses the space as a (panels of the workgroup) x (2 W + 1) u32 tile
@@ -114,18 +116,23 @@ __device__ __forceinline__ bool kbeats(int key, int best) {
 // K8 (template parameter of the register kernels): the keys carry their feature index, so the argmax
 // selects ONE register per feature (the key) instead of two (key and index).  Layout: remaining in
 // the high half, need = min - selected as a signed byte in bits 0-7, and the index in bits 8-15
-// stored as idx - [need < 0]: the packed 16-bit decrement of delete_person borrows from the index
-// byte exactly once, when need crosses 0 -> -1 (need only decreases), so idx = (byte 1 + [need < 0])
-// mod 256 holds throughout.  The products read the need byte and the remaining half through SDWA
+// stored as idx + 1 - [need < 0]: the packed 16-bit decrement of delete_person borrows from the index
+// byte exactly once, when need crosses 0 -> -1 (need only decreases), so idx + 1 = byte 1 + [need < 0]
+// holds throughout and never wraps (one bfe of the sign bit plus one add reading byte 1; the users
+// fold the + 1 into their row base pointer).  The products read the need byte and the remaining half through SDWA
 // selects, as the 16-bit form does.  Taken when every need stays in [-127, 127] (csa_instance::need8;
 // sf_e, example_large_200), else the 16-bit keys (K8 = false) -- sf_e 270.0 -> 273.9 M panels/s.
 typedef signed char schar4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int k8need(int key) { return (int)__builtin_bit_cast(schar4_t, key).x; }
 __device__ __forceinline__ int k8rem(int key) { return (int)as_s2(key).y; }
 __device__ __forceinline__ int k8pack(int need, int rem, int idx) {
-    return (int)(((uint32_t)rem << 16) | ((uint32_t)(idx - (need < 0)) & 0xFFu) << 8 | ((uint32_t)need & 0xFFu));
+    return (int)(((uint32_t)rem << 16) | ((uint32_t)(idx + 1 - (need < 0)) & 0xFFu) << 8 | ((uint32_t)need & 0xFFu));
 }
-__device__ __forceinline__ int k8idx(int key) { return (int)(((uint32_t)key >> 8) + (uint32_t)(k8need(key) < 0)) & 0xFF; }
+// idx + 1 (see above)
+__device__ __forceinline__ int k8idx1(int key) { return (int)((((uint32_t)key >> 8) & 0xFFu) + (((uint32_t)key >> 7) & 1u)); }
+// the argmax start value: need -100, remaining 1 (legacy.py:125); K8: index 0 (byte 1 = 0 + 1 - [need < 0])
+template <bool K8>
+constexpr int kDrawSentinel = K8 ? (1 << 16) | 0x009C : (1 << 16) | 0xFF9C;
 __device__ __forceinline__ bool k8beats(int key, int best) {
     return k8need(key) * k8rem(best) > k8need(best) * k8rem(key);
 }
@@ -282,8 +289,9 @@ __device__ __forceinline__ void emit_xt_rows(const DrawArgs &A, const uint32_t *
 }
 
 // FN: features (padded, <= 32); WN: pool words (padded, <= 32, even per lane); SK: kept in the
-// signature for the launcher (the holder scan reads all WN / 2 row words in one round trip)
-template <int FN, int WN, int SK, bool K8>
+// signature for the launcher (the holder scan reads all WN / 2 row words in one round trip); NP: slack
+// bit planes kept (the instance's largest max - selected < 2^NP, csa_instance::max_slack)
+template <int FN, int WN, int SK, int NP, bool K8>
 __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(DrawArgs A) {
     constexpr int G = 2;
     constexpr int LS = WN + 1;        // odd row stride: lanes reading different rows hit different banks
@@ -291,11 +299,11 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
     constexpr int FPL = FN / G, WPL = WN / G;
     // built for F > 16 only (FN = 32: F <= 16 takes draw_solo_kernel), so a lane holds 16 features and
     // the full test is always the bit-sliced slack planes
-    static_assert(FN == 32 && WN <= 32 && (WN % 2) == 0 && SK >= 1, "lane draw layout");
+    static_assert(FN == 32 && WN <= 32 && (WN % 2) == 0 && SK >= 1 && NP >= 1 && NP <= 8, "lane draw layout");
     extern __shared__ uint64_t smem[];
     const int F = A.F, W = A.W, n = A.n, k = A.k;
     uint64_t *fm = smem;
-    // row f word t = fm row f word WN-1-t (the second lane's order).  Skewed by 8 words: FN * LS words is
+    // row f word t = fm row f word WN-1-t, bit-reversed (the second lane's mirrored order).  Skewed by 8 words: FN * LS words is
     // a multiple of 32 dwords, so without it the two lanes of a pair read the same bank pair of the
     // 32 a ds_read2_b64 uses (a 2-way conflict on every scan read); 8 words put them 16 banks apart
     uint64_t *fm_rev = fm + FN * LS + 8;
@@ -303,7 +311,7 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
     int32_t *need0_s = reinterpret_cast<int32_t *>(pm + ((n + 3) & ~3));
     int32_t *rem0_s = need0_s + FN, *mnx_s = need0_s + 2 * FN;  // mnx_s: the slack bit planes
     uint64_t *pres0_s = reinterpret_cast<uint64_t *>(need0_s + 4 * FN);
-    uint64_t *pres0_rev = pres0_s + WN;  // word t = pool word WN-1-t
+    uint64_t *pres0_rev = pres0_s + WN;  // word t = pool word WN-1-t, bit-reversed
     uint64_t *slot_all = pres0_s + 2 * WN;
     int32_t *dec_all = reinterpret_cast<int32_t *>(slot_all + (kLaneThreads / 64) * kLaneSlots * WN);
 
@@ -314,7 +322,7 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
         const bool lf = f < F && ((live >> f) & 1u);
         fm[t] = (lf && w < W) ? A.featmask[f * A.Ws + w] : 0ull;
         const int wr = WN - 1 - w;
-        fm_rev[t] = (lf && w < WN && wr < W) ? A.featmask[f * A.Ws + wr] : 0ull;
+        fm_rev[t] = (lf && w < WN && wr < W) ? __brevll(A.featmask[f * A.Ws + wr]) : 0ull;
     }
     for (int t = threadIdx.x; t < n; t += blockDim.x) pm[t] = A.pmask[t] & live;
     for (int t = threadIdx.x; t < FN; t += blockDim.x) {
@@ -327,8 +335,9 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
         }
     }
     // attempt-start "slack" = max - selected of each lane's features, bit-sliced: mnx_s[8 glane + i]
-    // bit j = bit i of the slack of feature glane * FPL + j (the host routes max - selected > 255
-    // elsewhere; dead and padding features get 255 and are never picked, so never reach 0)
+    // bit j = bit i of the slack of feature glane * FPL + j; the lanes keep planes 0..NP-1 (the host
+    // picks NP with every slack < 2^NP and routes max - selected > 255 elsewhere; dead and padding
+    // features get all ones and are never picked, so never reach 0)
     for (int t = threadIdx.x; t < 16; t += blockDim.x) {
         const int h = t >> 3, bit = t & 7;
         uint32_t P = 0;
@@ -342,15 +351,16 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
     }
     for (int t = threadIdx.x; t < WN; t += blockDim.x) {
         pres0_s[t] = t < W ? A.present0[t] : 0ull;
-        pres0_rev[t] = WN - 1 - t < W ? A.present0[WN - 1 - t] : 0ull;
+        pres0_rev[t] = WN - 1 - t < W ? __brevll(A.present0[WN - 1 - t]) : 0ull;
     }
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int glane = lane & 1, gbase = lane & ~1;
     const int fbase = glane * FPL;
-    const uint64_t *fmx = glane ? fm_rev : fm;  // rows in this lane's word order
-    auto AW = [&](int j) -> int { return glane ? WN - 1 - j : j; };  // actual pool word of register j
+    const uint64_t *fmx = glane ? fm_rev : fm;  // rows in this lane's order
+    // agent of position m = 64 word + bit in this lane's order: poff + psgn m
+    const int poff = glane ? 64 * WN - 1 : 0, psgn = glane ? -1 : 1;
     uint64_t *slots = slot_all + (size_t)wave * kLaneSlots * WN;
     int32_t *decs = dec_all + wave * kLaneSlots * FN;
     const uint32_t key0 = (uint32_t)A.seed, key1 = (uint32_t)(A.seed >> 32);
@@ -367,9 +377,9 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
     uint64_t rm[WPL];  // remaining pool, this lane's words in its scan order
     // picks of steps 8c + 4 glane .. 8c + 4 glane + 3 (u16 each, two per dword), stored per 8 steps
     uint32_t pacc_lo = 0u, pacc_hi = 0u;
-    uint32_t sp[8];        // slack bit planes of this lane's features (see slack_s above)
+    uint32_t sp[NP];       // slack bit planes of this lane's features (see mnx_s above)
 #pragma unroll
-    for (int q = 0; q < 8; ++q) sp[q] = 0u;
+    for (int q = 0; q < NP; ++q) sp[q] = 0u;
     const int kpad = (k + 7) & ~7;
 #pragma unroll
     for (int j = 0; j < FPL; ++j) key[j] = 0;
@@ -400,7 +410,7 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                 for (int j = 0; j < FPL; ++j)  // K8: packed with its index at kernel start
                     key[j] = K8 ? need0_s[fbase + j] : kpack(need0_s[fbase + j], rem0_s[fbase + j]);
 #pragma unroll
-                for (int q = 0; q < 8; ++q) sp[q] = (uint32_t)mnx_s[8 * glane + q];
+                for (int q = 0; q < NP; ++q) sp[q] = (uint32_t)mnx_s[8 * glane + q];
 #pragma unroll
                 for (int j = 0; j < WPL; ++j) rm[j] = pres0_l[j];
                 started = true;
@@ -421,8 +431,7 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
         uint32_t fl = 0;  // the pick's features (this lane's share) that reached max
         LANE_REGION(step, 2, started);
         if (started) {
-            // need -100, remaining 1 (legacy.py:125); K8: index 0 (byte 0xFF = 0 - [need < 0])
-            constexpr int kSentinel = (1 << 16) | 0xFF9C;
+            constexpr int kSentinel = kDrawSentinel<K8>;
             int best, bi;
             if constexpr (K8) {
                 // two independent chains (features [0, H) and [H, FPL)) merged at the end (chain A wins
@@ -440,9 +449,9 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                 {  // the pair's DPP exchange: lane 0 holds the lower indices, so it wins ties
                     const int ob = partner<0>(best);
                     const int l = k8need(ob) * k8rem(best), r = k8need(best) * k8rem(ob);
-                    best = ((l > r) | ((l == r) & (glane != 0))) ? ob : best;
+                    best = l > r - glane ? ob : best;  // lane 1 also takes a tie (|products| < 2^23)
                 }
-                bi = k8idx(best);
+                bi = k8idx1(best);  // index + 1: the row base below is one row early
             } else {
                 // two independent chains (features [0, H) and [H, FPL)) merged at the end: each chain
                 // is a serial mul -> compare -> select dependency, so interleaving two of them fills
@@ -489,7 +498,7 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                 const uint32_t other_w = (uint32_t)partner<0>((int)mine_w);
                 const uint32_t word = ((it >> 2) & 1u) == (uint32_t)glane ? mine_w : other_w;
                 const int r = 1 + (int)__umulhi(word, (uint32_t)bd);  // randint(1, rem[f*]), legacy.py:149
-                const uint64_t *row = fmx + bi * LS;
+                const uint64_t *row = (K8 ? fmx - LS : fmx) + bi * LS;
                 // rank sought among this lane's words in its scan order
                 const int rr = glane ? bd - r + 1 : r;
                 uint64_t rw[WPL];  // every row read issued before the scan (one LDS round trip)
@@ -499,10 +508,14 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                 // kept (both masked words, the count before it), then one compare picks the word
                 // inside it -- the count / index selects once per two words (7.5 VALU per word
                 // instead of 9)
-                int acc = 0, base = 0, wsp = 0;
-                uint64_t ma = 0ull, mb = 0ull;
+                // (rr >= 1 on both lanes, so the first pair is always taken: it initialises the kept
+                // pair and the select chain starts at the second)
+                int base = 0, wsp = 0;
+                uint64_t ma = rm[0] & rw[0], mb = rm[1] & rw[1];
+                int acc = bcnt_acc((uint32_t)(ma >> 32), bcnt_acc((uint32_t)ma, 0));
+                acc = bcnt_acc((uint32_t)(mb >> 32), bcnt_acc((uint32_t)mb, acc));
 #pragma unroll
-                for (int j = 0; j < WPL; j += 2) {
+                for (int j = 2; j < WPL; j += 2) {
                     const uint64_t m0 = rm[j] & rw[j], m1 = rm[j + 1] & rw[j + 1];
                     const bool tk = acc < rr;
                     base = tk ? acc : base;
@@ -520,8 +533,8 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                 const uint64_t ms = second ? mb : ma;
                 const int ws = wsp + (int)second;
                 const int kin = hit ? rr - base - (second ? c0 : 0) : 1;
-                const int b = select_bit(ms, glane ? __popcll(ms) - kin + 1 : kin);
-                const int pl = hit ? AW(ws) * 64 + b : -1;
+                const int b = select_bit(ms, kin);
+                const int pl = hit ? poff + psgn * (ws * 64 + b) : -1;
                 const int p = max(pl, partner<0>(pl));
                 const uint32_t hb = pm[p] >> fbase;
                 {
@@ -534,17 +547,18 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                     // max - selected reaches 0: a bit-sliced decrement of the pick's features (two
                     // VALU per bit plane for all FPL features at once) and a zero test of the planes
                     // (~21 VALU instead of 2 per feature).  Only the pick's own features can have just
-                    // become full (an earlier full feature has no holder left); a feature that started
-                    // at max wraps past 0 to 255 -- never "== max" again, as in the reference.
+                    // become full (an earlier full feature has no holder left; no feature starts at max:
+                    // csa_instance::sel_over_max routes those elsewhere).
                     uint32_t bw = hb & 0xFFFFu;
                     const uint32_t picked = bw;
+                    uint32_t nz = 0u;
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {
+                    for (int q = 0; q < NP; ++q) {
                         const uint32_t t = sp[q];
                         sp[q] = t ^ bw;
-                        bw &= ~t;
+                        nz |= sp[q];
+                        if (q + 1 < NP) bw &= ~t;
                     }
-                    const uint32_t nz = sp[0] | sp[1] | sp[2] | sp[3] | sp[4] | sp[5] | sp[6] | sp[7];
                     fl = (picked & ~nz) << fbase;
                 }
                 LANE_REGION(update, 0, false);  // (runs with `pick`)
@@ -591,6 +605,27 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
             }
         }
         LANE_STAMP(1);  // the step: argmax, holder scan, select, decrements
+
+        // ---- the k-th pick: check_min_cats (legacy.py:160-168, analysis.py:155-159) now, and no
+        // cascade for a panel that passes -----------------------------------------------------------
+        // After the last pick nothing reads the pool or remaining again, except the rejection
+        // classifier below (need > 0 = remaining) of a pair with some need > 0.  A pair with every
+        // need <= 0 is accepted whatever its cascade would leave (it cannot raise legacy.py:55, and
+        // legacy.py:198-199 applies before the last step only), so its full features are dropped
+        // here; an under-quota pair cascades as ever when the statistics are wanted.  The branch is
+        // wave-uniform: an ordinary step pays the compare.
+        const bool last = started & (outcome == kContinue) & (s == k - 1);
+        if (__ballot(last) != 0ull) {
+            LANE_REGION(kcheck, 9, true);
+            bool u = false;
+#pragma unroll
+            for (int j = 0; j < FPL; ++j) u |= (K8 ? k8need(key[j]) : kneed(key[j])) > 0;
+            const bool under = max((int)u, partner<0>((int)u)) != 0;
+            if (last) {
+                outcome = under ? kReject : kAccept;
+                if (!(under && A.stats)) fl = 0u;
+            }
+        }
 
         // ---- delete_all_in_cat, wave-cooperative in rounds of kLaneSlots cascading pairs ---------
         uint64_t cb = __ballot(fl != 0u && glane == 0);
@@ -642,7 +677,7 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                 }
             }
             // rem[g] = popcount(pool & featmask[g]): lane = (feature g, word half); slot words
-            // WPL.. hold the second lane's words reversed, paired with fm_rev
+            // WPL.. hold the second lane's words mirrored, paired with fm_rev
             const int g = lane & 31, half = lane >> 5;
             const int w0 = half * WS;
             const uint64_t *frow = (half ? fm_rev - WS : fm) + (g < FN ? g : 0) * LS;
@@ -714,13 +749,7 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
         LANE_REGION(book, 0, false);
         // ---- bookkeeping: the k-th pick's min-quota check, restarts, accepted panels -------------
         if (started) {
-            if (outcome == kContinue && ++s == k) {  // check_min_cats (legacy.py:160-168, analysis.py:155-159)
-                LANE_REGION(kcheck, 9, true);
-                bool under = false;
-#pragma unroll
-                for (int j = 0; j < FPL; ++j) under |= (K8 ? k8need(key[j]) : kneed(key[j])) > 0;
-                outcome = max((int)under, partner<0>((int)under)) ? kReject : kAccept;
-            }
+            if (outcome == kContinue) ++s;  // (the k-th pick's outcome was set before the cascades)
             LANE_REGION(book, 0, false);
             if (outcome != kContinue) {
                 LANE_REGION(ending, 10, true);

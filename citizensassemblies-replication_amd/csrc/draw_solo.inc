@@ -45,11 +45,12 @@ __host__ __device__ inline size_t solo_lds_bytes(int FN, int WN, int n) {
 #define CSA_SOLO_OCC8 4
 #endif
 
-template <int FN, int WN, bool K8>
+// NP: slack bit planes kept (FN >= 16; the instance's largest max - selected < 2^NP, as draw_lane_kernel)
+template <int FN, int WN, int NP, bool K8>
 __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OCC) void draw_solo_kernel(DrawArgs A) {
     constexpr int LS = WN + 1;        // odd row stride
     constexpr bool kSlackPlanes = FN >= 16;
-    static_assert(FN <= 32 && WN <= 32 && (FN % 8) == 0 && (WN % 2) == 0, "solo draw layout");
+    static_assert(FN <= 32 && WN <= 32 && (FN % 8) == 0 && (WN % 2) == 0 && NP >= 1 && NP <= 8, "solo draw layout");
     extern __shared__ uint64_t smem[];
     const int F = A.F, W = A.W, n = A.n, k = A.k;
     uint64_t *fm = smem;
@@ -78,7 +79,8 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
         }
     }
     // FN >= 16: slack = max - selected of every feature, bit-sliced: mnx_s[i] bit j = bit i of the
-    // slack of feature j (dead and padding features 255, never picked); FN = 8: mnx_s[f] = min - max + 1
+    // slack of feature j, planes 0..NP-1 kept (dead and padding features all ones, never picked);
+    // FN = 8: mnx_s[f] = min - max + 1
     if constexpr (!kSlackPlanes) {
         for (int t = threadIdx.x; t < FN; t += blockDim.x) {
             const bool v = t < F && ((live >> t) & 1u);
@@ -111,9 +113,9 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
     int key[FN];       // packed (need, remaining) per feature
     uint64_t rm[WN];   // remaining pool
     uint64_t pacc = 0ull;  // picks of steps 4c .. 4c + 3 (u16 each), stored per 4 steps
-    uint32_t sp[8];        // slack bit planes (FN >= 16)
+    uint32_t sp[NP];       // slack bit planes (FN >= 16)
 #pragma unroll
-    for (int q = 0; q < 8; ++q) sp[q] = 0u;
+    for (int q = 0; q < NP; ++q) sp[q] = 0u;
     const int kpad = (k + 7) & ~7;
 #pragma unroll
     for (int j = 0; j < FN; ++j) key[j] = 0;
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                     key[j] = K8 ? need0_s[j] : kpack(need0_s[j], rem0_s[j]);  // K8: packed at kernel start
                 if constexpr (kSlackPlanes) {
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) sp[q] = (uint32_t)mnx_s[q];
+                    for (int q = 0; q < NP; ++q) sp[q] = (uint32_t)mnx_s[q];
                 }
 #pragma unroll
                 for (int j = 0; j < WN; ++j) rm[j] = pres0_s[j];
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
         int outcome = kContinue;
         uint32_t fl = 0;  // the pick's features that reached max
         if (started) {
-            constexpr int kSentinel = (1 << 16) | 0xFF9C;  // need -100, remaining 1 (legacy.py:125)
+            constexpr int kSentinel = kDrawSentinel<K8>;  // need -100, remaining 1 (legacy.py:125)
             // four independent chains over consecutive feature ranges, merged in index order (ties
             // keep the lower chain: the first maximum, as the single strict-'>' chain)
             constexpr int Q = FN / 4;
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                 }
                 const int ba = k8beats(b1, b0) ? b1 : b0, bb = k8beats(b3, b2) ? b3 : b2;
                 best = k8beats(bb, ba) ? bb : ba;
-                bi = k8idx(best);
+                bi = k8idx1(best);  // index + 1: the row base below is one row early
             } else {
                 int b0 = kSentinel, i0 = 0, b1 = kSentinel, i1 = Q, b2 = kSentinel, i2 = 2 * Q, b3 = kSentinel, i3 = 3 * Q;
 #pragma unroll
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                 const int q = (int)(it & 3u);  // == s & 3 for every running lane
                 const uint32_t word = q == 0 ? x0 : (q == 1 ? x1 : (q == 2 ? x2 : x3));
                 const int r = 1 + (int)__umulhi(word, (uint32_t)bd);  // randint(1, rem[f*]), legacy.py:149
-                const uint64_t *row = fm + bi * LS;
+                const uint64_t *row = (K8 ? fm - LS : fm) + bi * LS;
                 // forward scan over word pairs: the pair whose preceding holder count is < r is kept
                 // (both masked words and the count before it); row reads in batches of RB words
                 int acc = 0, base = 0, wsp = 0;
@@ -260,13 +262,14 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                     constexpr uint32_t kFnMask = FN >= 32 ? 0xFFFFFFFFu : (1u << FN) - 1u;
                     uint32_t bw = hb & kFnMask;
                     const uint32_t picked = bw;
+                    uint32_t nz = 0u;
 #pragma unroll
-                    for (int qq = 0; qq < 8; ++qq) {
+                    for (int qq = 0; qq < NP; ++qq) {
                         const uint32_t t = sp[qq];
                         sp[qq] = t ^ bw;
-                        bw &= ~t;
+                        nz |= sp[qq];
+                        if (qq + 1 < NP) bw &= ~t;
                     }
-                    const uint32_t nz = sp[0] | sp[1] | sp[2] | sp[3] | sp[4] | sp[5] | sp[6] | sp[7];
                     fl = picked & ~nz;
                 } else {
                     uint32_t em = 0;
@@ -294,6 +297,20 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                     *reinterpret_cast<uint64_t *>(A.picks16 + off) = pacc;
                     pacc = 0ull;
                 }
+            }
+        }
+
+        // ---- the k-th pick: check_min_cats (legacy.py:160-168, analysis.py:155-159) now, and no
+        // cascade for a panel that passes (see draw_lane_kernel): an under-quota panel still cascades
+        // when the statistics are wanted
+        const bool last = started & (outcome == kContinue) & (s == k - 1);
+        if (__ballot(last) != 0ull) {
+            bool under = false;
+#pragma unroll
+            for (int j = 0; j < FN; ++j) under |= (K8 ? k8need(key[j]) : kneed(key[j])) > 0;
+            if (last) {
+                outcome = under ? kReject : kAccept;
+                if (!(under && A.stats)) fl = 0u;
             }
         }
 
@@ -408,12 +425,7 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
 
         // ---- bookkeeping: the k-th pick's min-quota check, restarts, accepted panels -------------
         if (started) {
-            if (outcome == kContinue && ++s == k) {  // check_min_cats (legacy.py:160-168, analysis.py:155-159)
-                bool under = false;
-#pragma unroll
-                for (int j = 0; j < FN; ++j) under |= (K8 ? k8need(key[j]) : kneed(key[j])) > 0;
-                outcome = under ? kReject : kAccept;
-            }
+            if (outcome == kContinue) ++s;  // (the k-th pick's outcome was set before the cascades)
             if (outcome != kContinue) {
                 const uint64_t panel = A.panel_begin + i;
                 started = false;  // the next attempt / panel starts at the next iteration it = 0 mod 4

@@ -254,6 +254,21 @@ __global__ __launch_bounds__(kWideThreads, 4) void draw_wide_kernel(DrawArgs A) 
             }
         }
 
+        // ---- the k-th pick: check_min_cats (legacy.py:160-168, analysis.py:155-159) now, and no
+        // cascade for a panel that passes (see draw_lane_kernel): an under-quota panel still cascades
+        // when the statistics are wanted
+        const bool last = started & (outcome == kContinue) & (s == k - 1);
+        if (__ballot(last) != 0ull) {
+            bool u = false;
+#pragma unroll
+            for (int j = 0; j < FPL; ++j) u |= kneed(key[j]) > 0;
+            const bool under = wmax<G>((int)u) != 0;
+            if (last) {
+                outcome = under ? kReject : kAccept;
+                if (!(under && A.stats)) fl = 0ull;
+            }
+        }
+
         // ---- delete_all_in_cat, wave-cooperative in rounds of kWideSlots cascading groups --------
         uint64_t cb = __ballot((fl != 0ull) && glane == 0);
         while (cb) {
@@ -383,12 +398,7 @@ __global__ __launch_bounds__(kWideThreads, 4) void draw_wide_kernel(DrawArgs A) 
 
         // ---- bookkeeping: the k-th pick's min-quota check, restarts, accepted panels -------------
         if (started) {
-            if (outcome == kContinue && ++s == k) {  // check_min_cats (legacy.py:160-168, analysis.py:155-159)
-                bool under = false;
-#pragma unroll
-                for (int j = 0; j < FPL; ++j) under |= kneed(key[j]) > 0;
-                outcome = wmax<G>((int)under) ? kReject : kAccept;
-            }
+            if (outcome == kContinue) ++s;  // (the k-th pick's outcome was set before the cascades)
             if (outcome != kContinue) {
                 const uint64_t panel = A.panel_begin + i;
                 started = false;

@@ -258,7 +258,7 @@ int csa_panel_hash_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W,
                          void *stream);
 
 /* Name of the draw kernel csa_draw_async launches for this instance and k
- * (e.g. "draw_lane_kernel<32, 28, 14>"), for matching profiler output. */
+ * (e.g. "draw_lane_kernel<32, 28, 14, 7, true>"), for matching profiler output. */
 int csa_draw_kernel_name(const csa_instance *inst, int32_t k, char *buf, uint64_t len);
 
 /* Bit-transpose + per-person count.  Panels (n_panels*W) -> d_xt, the

@@ -4,7 +4,7 @@ and what it should cost, against the measured kernel time.
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -DCSA_LANE_STAMPS \\
         -o /tmp/csa_stamps.s citizensassemblies-replication_amd/csrc/csa_legacy.hip
     python tools/valu_budget.py /tmp/csa_stamps.s profiles/r04_valu_budget/lane_stamps_sf_e_110.json \\
-        [--pmc profiles/pmc_sf_e_110.json] [--kernel draw_lane_kernelILi32ELi28ELi14E]
+        [--pmc profiles/pmc_sf_e_110.json] [--kernel draw_lane_kernelILi32ELi28ELi14ELi7E]
 
 The CSA_LANE_STAMPS build marks the regions of the step loop with asm comments (";@region NAME") and
 counts, per wave, how often each region runs (tools/lane_stamps.py on the GPU box: a region counts
@@ -80,7 +80,7 @@ def main():
     ap.add_argument("asm")
     ap.add_argument("stamps", help="tools/lane_stamps.py JSON (region_runs_per_wave, ms, panels, waves)")
     ap.add_argument("--pmc", help="profiles/pmc_<config>.json (draw_issue: VALU per panel, clock)")
-    ap.add_argument("--kernel", default="draw_lane_kernelILi32ELi28ELi14ELb1E")
+    ap.add_argument("--kernel", default="draw_lane_kernelILi32ELi28ELi14ELi7ELb1E")
     ap.add_argument("--panels-per-wave", type=int, default=32)
     ap.add_argument("--out")
     args = ap.parse_args()
