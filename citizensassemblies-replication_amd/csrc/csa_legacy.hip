@@ -145,6 +145,8 @@ struct DrawArgs {
     // npad persons each) or null
     uint32_t *xt;
     int32_t npad;
+    // draw_lane_kernel / draw_solo_kernel: the attempt-start tables in their LDS layout (draw_image_build)
+    const uint64_t *image;
 };
 
 // ---- sub-wave group primitives ------------------------------------------------------------
@@ -625,7 +627,9 @@ __device__ __forceinline__ uint32_t xt_dpp(uint32_t v) {
 }
 __device__ __forceinline__ uint32_t xt_merge(uint32_t x, uint32_t y, uint32_t keep, uint32_t rot) {
     const uint32_t t = __builtin_amdgcn_alignbit(y, y, rot);  // y rotated right by rot
-    return (keep & x) | (~keep & t);                        // v_bfi
+    // keep ? x : t, one instruction: written as (keep & x) | (~keep & t) the compiler merges the masks of
+    // consecutive stages and issues 45 VALU per transpose for the 30 of the stage list above
+    return __builtin_amdgcn_bitop3_b32(keep, x, t, 0xCA);
 }
 __device__ __forceinline__ void wave_transpose64(uint32_t &lo, uint32_t &hi, const XtLane &c) {
     {  // s = 32
@@ -1758,6 +1762,9 @@ struct csa_instance {
     int32_t *d_fmin = nullptr, *d_fmax = nullptr, *d_sel0 = nullptr, *d_rem0 = nullptr;
     uint64_t *d_present0 = nullptr;
     uint32_t *d_pmask = nullptr;  // n person feature masks (F <= 32 only)
+    // the register kernels' attempt-start tables in their LDS layout (draw_image_build: rebuilt with the
+    // start state; null when neither register kernel fits the instance)
+    uint64_t *d_image = nullptr;
     int32_t *d_addr_next = nullptr;  // same-address rings (csa_instance_set_address) or null
     int32_t max_abs = 0;  // max |fmin| / |sel0| bound for the cross-multiplication range check
     bool zero_max_min = false;  // some feature has max 0 and min > 0 (draw_batch_kernel excludes it)
@@ -1972,6 +1979,16 @@ int pow2_ceil_int(int x) {
     return p;
 }
 
+// FN / WN of the register kernel an instance's shape takes (lane: 16 < F <= 32, solo: F <= 16); false
+// when neither is built for it
+bool reg_kernel_shape(const csa_instance *I, bool &lane, int &fn, int &wn) {
+    if (I->F > 32 || I->W > 32 || !I->d_pmask) return false;
+    lane = I->F > 16;
+    fn = std::max(8, pow2_ceil_int(I->F));
+    wn = I->W <= 4 ? 4 : I->W <= 8 ? 8 : I->W <= 16 ? 16 : I->W <= 28 ? 28 : 32;
+    return true;
+}
+
 // Batch draws: draw_solo_kernel (1 lane per panel) or draw_lane_kernel (2 lanes per panel, 32
 // panels per wavefront) when the instance fits -- F <= 32, W <= 32, no max = 0 < min feature, |min|, |selected| < 2^15 (16-bit packed
 // need / remaining) and no feature starting above max ("selected == max" is tested as
@@ -2001,8 +2018,8 @@ int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
     c.G = choice;
     if (choice == 1) {
         c.solo = true;
-        c.FPL = std::max(8, pow2_ceil_int(I->F));
-        c.WPL = I->W <= 4 ? 4 : I->W <= 8 ? 8 : I->W <= 16 ? 16 : I->W <= 28 ? 28 : 32;
+        bool lane_shape;
+        reg_kernel_shape(I, lane_shape, c.FPL, c.WPL);
         c.k8 = I->need8;
         c.np = c.FPL >= 16 ? slack_planes(I->max_slack) : 8;
         c.fn = solo_fn(c.FPL, c.WPL, c.k8, c.np);
@@ -2020,8 +2037,8 @@ int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
     }
     if (choice == 2) {
         c.lane = true;
-        c.FPL = std::max(8, pow2_ceil_int(I->F));
-        c.WPL = I->W <= 4 ? 4 : I->W <= 8 ? 8 : I->W <= 16 ? 16 : I->W <= 28 ? 28 : 32;
+        bool lane_shape;
+        reg_kernel_shape(I, lane_shape, c.FPL, c.WPL);
         c.k8 = I->need8;
         c.np = slack_planes(I->max_slack);
         c.fn = lane_fn(c.FPL, c.WPL, c.k8, c.np);
@@ -2037,6 +2054,89 @@ int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
     if (!c.fn)
         return fail(CSA_E_UNSUPPORTED, "no draw kernel for F=%d n=%d (G=%d needs FPL=%d WPL=%d)", I->F, I->n, c.G,
                     c.FPL, c.WPL);
+    return CSA_OK;
+}
+
+// The register kernels' attempt-start tables, built on the host from the instance and its start state
+// (I->sel0, I->rem0h, I->present0h, I->need8) and uploaded as one image in the kernels' LDS layout
+// (draw_image_layout, draw_lane.inc): called when the instance is created and whenever
+// csa_instance_set_state changes the start state.  A feature with min = max = 0 is removed (zero rows,
+// no person-mask bit, need = remaining = 0, all-ones slack); padding features likewise.
+int draw_image_build(csa_instance *I) {
+    bool lane = false;
+    int FN = 0, WN = 0;
+    if (!reg_kernel_shape(I, lane, FN, WN)) return CSA_OK;
+    const int F = I->F, W = I->W, n = I->n, LS = WN + 1;
+    const DrawImage L = draw_image_layout(lane, FN, WN, n);
+    std::vector<uint32_t> img((size_t)2 * L.words, 0u);
+    auto put64 = [&](int word, uint64_t v) {
+        img[2 * (size_t)word] = (uint32_t)v;
+        img[2 * (size_t)word + 1] = (uint32_t)(v >> 32);
+    };
+    auto brev64 = [](uint64_t x) {
+        uint64_t r = 0;
+        for (int b = 0; b < 64; ++b) r |= ((x >> b) & 1ull) << (63 - b);
+        return r;
+    };
+    uint32_t live = 0;  // features with max > 0
+    for (int f = 0; f < F; ++f) live |= (uint32_t)(I->fmax[f] != 0) << f;
+    auto alive = [&](int f) { return f < F && ((live >> f) & 1u); };
+    for (int f = 0; f < F; ++f) {
+        if (!alive(f)) continue;
+        const uint64_t *row = I->featmask.data() + (size_t)f * I->Ws;
+        for (int w = 0; w < W; ++w) put64(f * LS + w, row[w]);
+        // the second lane's order: word t = word WN-1-t, bit-reversed
+        for (int t = 0; lane && t < WN; ++t)
+            if (WN - 1 - t < W) put64(L.fm_rev + f * LS + t, brev64(row[WN - 1 - t]));
+    }
+    for (int p = 0; p < n; ++p) {
+        uint32_t m = 0;
+        for (int c = 0; c < I->C; ++c) m |= 1u << I->pf[(size_t)p * I->C + c];
+        img[2 * (size_t)L.pm + p] = m & live;
+    }
+    uint32_t *need0 = img.data() + 2 * (size_t)L.need0, *rem0 = need0 + FN, *mnx = need0 + 2 * FN;
+    const int32_t *rem = I->rem0h.empty() ? I->pool.data() : I->rem0h.data();
+    for (int t = 0; t < FN; ++t) {
+        const int need = alive(t) ? I->fmin[t] - I->sel0[t] : 0, rm = alive(t) ? rem[t] : 0;
+        if (I->need8) {  // the K8 kernels: keys packed with their index (k8pack)
+            need0[t] = (uint32_t)k8pack(need, rm, t);
+        } else {
+            need0[t] = (uint32_t)need;
+            rem0[t] = (uint32_t)rm;
+        }
+    }
+    if (FN >= 16) {
+        // slack = max - selected, bit-sliced: plane i of the lane kernel's half h (solo: one half of FN
+        // features) at mnx[8 h + i], bit j = bit i of the slack of feature h FPL + j
+        const int halves = lane ? 2 : 1, FPL = FN / halves;
+        for (int h = 0; h < halves; ++h)
+            for (int bit = 0; bit < 8; ++bit) {
+                uint32_t P = 0;
+                for (int j = 0; j < FPL; ++j) {
+                    const int f = h * FPL + j;
+                    const int sl = alive(f) ? I->fmax[f] - I->sel0[f] : 255;
+                    P |= (uint32_t)((sl >> bit) & 1) << j;
+                }
+                mnx[8 * h + bit] = P;
+            }
+    } else {  // draw_solo_kernel, FN = 8: full <=> need < min - max + 1
+        for (int t = 0; t < FN; ++t) mnx[t] = (uint32_t)(alive(t) ? I->fmin[t] - I->fmax[t] + 1 : -(1 << 30));
+    }
+    for (int t = 0; t < WN; ++t) {
+        auto pres = [&](int w) -> uint64_t {
+            if (w >= W) return 0ull;
+            if (!I->present0h.empty()) return I->present0h[w];
+            return w < n / 64 ? ~0ull : (1ull << (n & 63)) - 1ull;  // everyone (the last word: n mod 64 > 0 here)
+        };
+        put64(L.pres0 + t, pres(t));
+        if (lane) put64(L.pres0_rev + t, brev64(pres(WN - 1 - t)));
+    }
+    ScopedDevice sd(I->device);
+    if (!I->d_image) {
+        int rc = dalloc(&I->d_image, (size_t)L.words);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemcpy(I->d_image, img.data(), (size_t)L.words * 8, hipMemcpyHostToDevice));
     return CSA_OK;
 }
 
@@ -2168,6 +2268,8 @@ int launch_draw(const csa_instance *I, int32_t k, uint64_t seed, uint64_t panel_
     A.present_out = d_present_out;
     A.xt = nullptr;
     A.npad = ((I->n + 255) / 256) * 256;  // csa_xt_pad
+    A.image = I->d_image;
+    if ((cfg.lane || cfg.solo) && !A.image) return fail(CSA_E_INVALID, "the instance has no draw image");
     if (d_picks_ext && !cfg.picks()) return fail(CSA_E_UNSUPPORTED, "this instance does not take the pick-list draw");
     csa_instance *M = const_cast<csa_instance *>(I);  // the lane kernel's pick-list scratch
     if (d_picks_ext)
@@ -2460,6 +2562,10 @@ int csa_instance_create(int32_t n, int32_t C, int32_t F, const int32_t *person_f
         csa_instance_destroy(I);
         return fail(CSA_E_HIP, "instance upload: %s", hipGetErrorString(e));
     }
+    if ((rc = draw_image_build(I))) {
+        csa_instance_destroy(I);
+        return rc;
+    }
     *out = I;
     return CSA_OK;
 }
@@ -2479,6 +2585,7 @@ void csa_instance_destroy(csa_instance *I) {
     if (I->d_rem0) (void)hipFree(I->d_rem0);
     if (I->d_present0) (void)hipFree(I->d_present0);
     if (I->d_pmask) (void)hipFree(I->d_pmask);
+    if (I->d_image) (void)hipFree(I->d_image);
     if (I->d_addr_next) (void)hipFree(I->d_addr_next);
     if (I->d_picks16) (void)hipFree(I->d_picks16);
     if (I->d_stats) (void)hipFree(I->d_stats);
@@ -2585,18 +2692,18 @@ int csa_instance_set_state(csa_instance *I, const int32_t *sel, const int32_t *r
         if (I->fmax[f] > 0) I->max_slack = std::max(I->max_slack, I->fmax[f] - s);
     }
     I->max_abs = mx;
-    update_need8(I);
     if (present)
         for (int w = 0; w < I->W; ++w)
             if (present[w] & ~all[w]) return fail(CSA_E_INVALID, "present mask has bits beyond n");
     HIPCHK(hipMemcpy(I->d_sel0, sel ? sel : zeros.data(), I->F * 4, hipMemcpyHostToDevice));
     I->sel0.assign(sel ? sel : zeros.data(), (sel ? sel : zeros.data()) + I->F);
+    update_need8(I);  // (reads the new sel0)
     HIPCHK(hipMemcpy(I->d_rem0, rem ? rem : I->pool.data(), I->F * 4, hipMemcpyHostToDevice));
     if (I->W) HIPCHK(hipMemcpy(I->d_present0, present ? present : all.data(), I->W * 8, hipMemcpyHostToDevice));
     if (rem) I->rem0h.assign(rem, rem + I->F); else I->rem0h.clear();
     if (present) I->present0h.assign(present, present + I->W); else I->present0h.clear();
     ++I->gen;
-    return CSA_OK;
+    return draw_image_build(I);
 }
 
 int csa_instance_set_address(csa_instance *I, const int32_t *addr_next) {

@@ -125,7 +125,7 @@ __device__ __forceinline__ bool kbeats(int key, int best) {
 typedef signed char schar4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int k8need(int key) { return (int)__builtin_bit_cast(schar4_t, key).x; }
 __device__ __forceinline__ int k8rem(int key) { return (int)as_s2(key).y; }
-__device__ __forceinline__ int k8pack(int need, int rem, int idx) {
+__host__ __device__ inline int k8pack(int need, int rem, int idx) {
     return (int)(((uint32_t)rem << 16) | ((uint32_t)(idx + 1 - (need < 0)) & 0xFFu) << 8 | ((uint32_t)need & 0xFFu));
 }
 // idx + 1 (see above)
@@ -172,6 +172,50 @@ __device__ unsigned long long g_lane_stamps[24];
     } while (0)
 #endif
 
+// The register kernels' attempt-start tables -- feature rows (the lane kernel: also mirrored), person
+// masks, start keys, slack planes, start pool -- depend only on the instance and its start state, so the
+// host builds them once per state (draw_image_build, csa_legacy.hip) as one image in exactly the LDS
+// layout below, and a workgroup's prologue is a copy.  Offsets in 8-byte words from the start of the
+// dynamic LDS; need0 is followed by rem0 and the 2 FN words of slack planes (FN int32 each).
+struct DrawImage {
+    int fm_rev, pm, need0, pres0, pres0_rev, words;  // fm at 0; fm_rev / pres0_rev: the lane kernel only
+};
+__host__ __device__ constexpr DrawImage draw_image_layout(bool lane, int FN, int WN, int n) {
+    DrawImage L = {};
+    L.fm_rev = FN * (WN + 1) + 8;
+    L.pm = lane ? L.fm_rev + FN * (WN + 1) : FN * (WN + 1);
+    L.need0 = L.pm + ((n + 3) & ~3) / 2;
+    L.pres0 = L.need0 + 2 * FN;
+    L.pres0_rev = L.pres0 + WN;
+    L.words = L.pres0 + (lane ? 2 : 1) * WN;  // even: FN is a multiple of 8, WN even
+    return L;
+}
+// image -> LDS, 16 bytes per thread and trip; the trips of a batch issue their loads before the
+// first store (one memory round trip per batch), whole batches without a bounds test
+__device__ __forceinline__ void load_draw_image(uint64_t *smem, const uint64_t *image, int n16) {
+    constexpr int B = 4, T = 256;  // both register kernels run 256 threads
+    const uint4 *src = reinterpret_cast<const uint4 *>(image) + threadIdx.x;
+    uint4 *dst = reinterpret_cast<uint4 *>(smem) + threadIdx.x;
+    int base = 0;
+    for (; base + B * T <= n16; base += B * T) {
+        uint4 v[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) v[u] = src[base + u * T];
+#pragma unroll
+        for (int u = 0; u < B; ++u) dst[base + u * T] = v[u];
+    }
+    // the last batch is partial: its loads clamp their index to the image (no test), its stores test
+    const int left = n16 - base - (int)threadIdx.x;  // this thread's trips left: ceil(left / T) <= B
+    const uint4 *img = reinterpret_cast<const uint4 *>(image);
+    uint4 v[B];
+#pragma unroll
+    for (int u = 0; u < B; ++u) v[u] = img[min(base + u * T + (int)threadIdx.x, n16 - 1)];
+#pragma unroll
+    for (int u = 0; u < B; ++u)
+        if (u * T < left) dst[base + u * T] = v[u];
+    __syncthreads();
+}
+
 // Pick-list layout.  The fused pack (A.panels set) uses a chunked layout per workgroup of PPW panels:
 // chunk c (CH picks, steps c CH .. c CH + CH - 1) of the workgroup's panel p sits at u16 offset
 // ((wg nch + c) PPW + p) CH, nch = kpad / CH -- the lanes of a wave store their chunks of one step
@@ -206,44 +250,74 @@ __device__ __forceinline__ void pack_tile_rows(const DrawArgs &A, uint32_t *tile
     const int p0 = (int)(pb % PPW);
     // unit (c, r) of this tile: chunk c of the workgroup's panel p0 + r
     const unit_t *src = reinterpret_cast<const unit_t *>(A.picks16 + (wg * nch * PPW + p0) * CH);
-    const int nu = nch * kPackRows;
     __syncthreads();
-    constexpr int kChunks = 8;
-    for (int e0 = 0; e0 < nu; e0 += kChunks * kLaneThreads) {
-        unit_t v[kChunks];
+    // A thread keeps one row, r = thread mod kPackRows, and takes the chunks c = thread / kPackRows + kRowSets u:
+    // c is the same for a whole wave (kPackRows is a multiple of 64), so the tests on it are scalar
+    // branches and only the row test masks lanes.  A chunk below the k-th pick ORs its CH picks
+    // unconditionally; only the chunks that hold padding picks (steps >= k, stored as 0) test each pick.
+    constexpr int kChunks = 8, kRowSets = kLaneThreads / kPackRows;
+    static_assert(kPackRows % 64 == 0 && kLaneThreads % kPackRows == 0, "a wave's threads share their chunk index");
+    const int r = (int)(threadIdx.x & (kPackRows - 1));
+    const int cfirst = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kPackRows));
+    if (r < rows) {
+        uint32_t *trow = tile + r * R;
+        const unit_t *srow = src + r;
+        for (int c0 = cfirst; c0 < nch; c0 += kRowSets * kChunks) {
+            unit_t v[kChunks];
 #pragma unroll
-        for (int u = 0; u < kChunks; ++u) {
-            const int e = e0 + u * kLaneThreads + (int)threadIdx.x;
-            const int r = e & (kPackRows - 1), c = e >> 7;
-            if (e < nu && r < rows) v[u] = src[(uint64_t)c * PPW + r];
-        }
+            for (int u = 0; u < kChunks; ++u) {
+                const int c = c0 + kRowSets * u;
+                if (c < nch) v[u] = srow[(uint64_t)c * PPW];
+            }
 #pragma unroll
-        for (int u = 0; u < kChunks; ++u) {
-            const int e = e0 + u * kLaneThreads + (int)threadIdx.x;
-            const int r = e & (kPackRows - 1), c = e >> 7;
-            if (e < nu && r < rows) {
-                uint32_t w4[4];
-                if constexpr (CH == 8) {
-                    w4[0] = v[u].x; w4[1] = v[u].y; w4[2] = v[u].z; w4[3] = v[u].w;
-                } else {
-                    w4[0] = v[u].x; w4[1] = v[u].y; w4[2] = w4[3] = 0u;
-                }
+            for (int u = 0; u < kChunks; ++u) {
+                const int c = c0 + kRowSets * u;
+                if (c < nch) {
+                    uint32_t w4[4];
+                    if constexpr (CH == 8) {
+                        w4[0] = v[u].x; w4[1] = v[u].y; w4[2] = v[u].z; w4[3] = v[u].w;
+                    } else {
+                        w4[0] = v[u].x; w4[1] = v[u].y; w4[2] = w4[3] = 0u;
+                    }
+                    if ((c + 1) * CH <= k) {
 #pragma unroll
-                for (int h = 0; h < CH; ++h) {
-                    if (c * CH + h < k) {
-                        const uint32_t q = (h & 1) ? w4[h >> 1] >> 16 : w4[h >> 1] & 0xFFFFu;
-                        atomicOr(&tile[r * R + (q >> 5)], 1u << (q & 31));
+                        for (int h = 0; h < CH; ++h) {
+                            const uint32_t q = (h & 1) ? w4[h >> 1] >> 16 : w4[h >> 1] & 0xFFFFu;
+                            atomicOr(&trow[q >> 5], 1u << (q & 31));
+                        }
+                    } else {
+#pragma unroll
+                        for (int h = 0; h < CH; ++h) {
+                            if (c * CH + h < k) {
+                                const uint32_t q = (h & 1) ? w4[h >> 1] >> 16 : w4[h >> 1] & 0xFFFFu;
+                                atomicOr(&trow[q >> 5], 1u << (q & 31));
+                            }
+                        }
                     }
                 }
             }
         }
     }
     __syncthreads();
+    // rows stored coalesced: element t = r W + w for t = thread, thread + 256, ...; the row, the word and the
+    // tile address are carried from trip to trip (256 = dq W + dm, and a row's end adds R - 2 W = 1)
     uint64_t *dst = A.panels + pb * (uint64_t)W;
-    const float rw = 1.0f / (float)W;
-    for (int t = threadIdx.x; t < rows * W; t += blockDim.x) {
-        const int r = min(rows - 1, (int)(((float)t + 0.5f) * rw)), w = t - r * W;
-        dst[t] = (uint64_t)tile[r * R + 2 * w] | ((uint64_t)tile[r * R + 2 * w + 1] << 32);
+    {
+        const int nt = rows * W, dq = kLaneThreads / W, dm = kLaneThreads - dq * W, step = dq * R + 2 * dm;
+        int t = (int)threadIdx.x;
+        // thread / W by a float reciprocal: exact for thread < 256, W <= 32 (t + 0.5 is >= 0.5 / W from an integer multiple)
+        const int r0 = (int)(((float)t + 0.5f) * (1.0f / (float)W));
+        int w = t - r0 * W;
+        const uint32_t *tp = tile + r0 * R + 2 * w;
+        for (; t < nt; t += kLaneThreads) {
+            dst[t] = (uint64_t)tp[0] | ((uint64_t)tp[1] << 32);
+            w += dm;
+            tp += step;
+            if (w >= W) {
+                w -= W;
+                tp += 1;
+            }
+        }
     }
     if (A.hashes) {  // two lanes per panel (threads 2r, 2r + 1), the words alternating
         const int r = threadIdx.x >> 1, sub = threadIdx.x & 1;
@@ -268,23 +342,33 @@ __device__ __forceinline__ void pack_tile_rows(const DrawArgs &A, uint32_t *tile
 // register transpose (wave_transpose64, 30 VALU) per 64-panel block and 64-person word, written as
 // csa_transpose_count_async writes them (plane 0: panels 0-31 of the block, plane 1: 32-63; npad persons,
 // the padding words zero).  Read-only on the tile: the next pack_tile_rows starts with a barrier.
+// A wave takes the words w = wave, wave + NWAVES, ... of each block: the block and the word are
+// wave-uniform, so the stores are a scalar base plus the lane, the tile read steps one LDS address, and
+// a trip is the transpose plus that step.  The tile's rows past `rows` are zero (pack_tile_rows clears
+// all kPackRows and fills `rows`), so a partly empty block needs no row test; the padding words
+// (w >= W) are stored as zeros without a transpose.
 template <int NWAVES>
 __device__ __forceinline__ void emit_xt_rows(const DrawArgs &A, const uint32_t *tile, uint64_t pb, int rows, int lane,
                                              int wave) {
     const XtLane tc = xt_lane_consts(lane);
-    const int W = A.W, R = 2 * W + 1, nwd = A.npad / 64, nb = (rows + 63) / 64;
-    const uint64_t b0 = pb / 64;
-    for (int e = wave; e < nb * nwd; e += NWAVES) {
-        const int blk = e / nwd, w = e - blk * nwd, r = 64 * blk + lane;
-        uint32_t lo = 0u, hi = 0u;
-        if (w < W && r < rows) {
-            lo = tile[r * R + 2 * w];
-            hi = tile[r * R + 2 * w + 1];
+    const int W = A.W, R = 2 * W + 1, npad = A.npad, nwd = npad / 64, nb = (rows + 63) / 64;
+    const int w0 = __builtin_amdgcn_readfirstlane(wave);
+    for (int blk = 0; blk < nb; ++blk) {
+        const uint32_t *trow = tile + (64 * blk + lane) * R + 2 * w0;
+        // the block's two planes (wave-uniform) and this lane's byte offset in them, stepped per word
+        char *xlo = reinterpret_cast<char *>(A.xt + 2 * (pb / 64 + blk) * (uint64_t)npad), *xhi = xlo + 4 * (size_t)npad;
+        uint32_t off = 4u * (uint32_t)(64 * w0 + lane);
+        int w = w0;
+        for (; w < W; w += NWAVES, trow += 2 * NWAVES, off += 256u * NWAVES) {
+            uint32_t lo = trow[0], hi = trow[1];
+            wave_transpose64(lo, hi, tc);
+            *reinterpret_cast<uint32_t *>(xlo + off) = lo;
+            *reinterpret_cast<uint32_t *>(xhi + off) = hi;
         }
-        wave_transpose64(lo, hi, tc);
-        uint32_t *x32 = A.xt + 2 * (b0 + blk) * (uint64_t)A.npad + 64 * w + lane;
-        x32[0] = lo;
-        x32[A.npad] = hi;
+        for (; w < nwd; w += NWAVES, off += 256u * NWAVES) {
+            *reinterpret_cast<uint32_t *>(xlo + off) = 0u;
+            *reinterpret_cast<uint32_t *>(xhi + off) = 0u;
+        }
     }
 }
 
@@ -301,59 +385,26 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
     // the full test is always the bit-sliced slack planes
     static_assert(FN == 32 && WN <= 32 && (WN % 2) == 0 && SK >= 1 && NP >= 1 && NP <= 8, "lane draw layout");
     extern __shared__ uint64_t smem[];
-    const int F = A.F, W = A.W, n = A.n, k = A.k;
+    const int n = A.n, k = A.k;
+    const DrawImage L = draw_image_layout(true, FN, WN, n);
     uint64_t *fm = smem;
     // row f word t = fm row f word WN-1-t, bit-reversed (the second lane's mirrored order).  Skewed by 8 words: FN * LS words is
     // a multiple of 32 dwords, so without it the two lanes of a pair read the same bank pair of the
     // 32 a ds_read2_b64 uses (a 2-way conflict on every scan read); 8 words put them 16 banks apart
-    uint64_t *fm_rev = fm + FN * LS + 8;
-    uint32_t *pm = reinterpret_cast<uint32_t *>(fm_rev + FN * LS);
-    int32_t *need0_s = reinterpret_cast<int32_t *>(pm + ((n + 3) & ~3));
+    uint64_t *fm_rev = fm + L.fm_rev;
+    uint32_t *pm = reinterpret_cast<uint32_t *>(fm + L.pm);
+    int32_t *need0_s = reinterpret_cast<int32_t *>(fm + L.need0);
     int32_t *rem0_s = need0_s + FN, *mnx_s = need0_s + 2 * FN;  // mnx_s: the slack bit planes
-    uint64_t *pres0_s = reinterpret_cast<uint64_t *>(need0_s + 4 * FN);
-    uint64_t *pres0_rev = pres0_s + WN;  // word t = pool word WN-1-t, bit-reversed
-    uint64_t *slot_all = pres0_s + 2 * WN;
+    uint64_t *pres0_s = fm + L.pres0;
+    uint64_t *pres0_rev = fm + L.pres0_rev;  // word t = pool word WN-1-t, bit-reversed
+    uint64_t *slot_all = fm + L.words;
     int32_t *dec_all = reinterpret_cast<int32_t *>(slot_all + (kLaneThreads / 64) * kLaneSlots * WN);
 
-    uint32_t live = 0;  // features with max > 0 (dead min = max = 0 features are removed)
-    for (int f = 0; f < F; ++f) live |= (uint32_t)(A.fmax[f] != 0) << f;
-    for (int t = threadIdx.x; t < FN * LS; t += blockDim.x) {
-        const int f = t / LS, w = t - f * LS;
-        const bool lf = f < F && ((live >> f) & 1u);
-        fm[t] = (lf && w < W) ? A.featmask[f * A.Ws + w] : 0ull;
-        const int wr = WN - 1 - w;
-        fm_rev[t] = (lf && w < WN && wr < W) ? __brevll(A.featmask[f * A.Ws + wr]) : 0ull;
-    }
-    for (int t = threadIdx.x; t < n; t += blockDim.x) pm[t] = A.pmask[t] & live;
-    for (int t = threadIdx.x; t < FN; t += blockDim.x) {
-        const bool v = t < F && ((live >> t) & 1u);
-        if constexpr (K8) {
-            need0_s[t] = k8pack(v ? A.fmin[t] - A.sel0[t] : 0, v ? A.rem0[t] : 0, t);
-        } else {
-            need0_s[t] = v ? A.fmin[t] - A.sel0[t] : 0;
-            rem0_s[t] = v ? A.rem0[t] : 0;
-        }
-    }
-    // attempt-start "slack" = max - selected of each lane's features, bit-sliced: mnx_s[8 glane + i]
-    // bit j = bit i of the slack of feature glane * FPL + j; the lanes keep planes 0..NP-1 (the host
-    // picks NP with every slack < 2^NP and routes max - selected > 255 elsewhere; dead and padding
-    // features get all ones and are never picked, so never reach 0)
-    for (int t = threadIdx.x; t < 16; t += blockDim.x) {
-        const int h = t >> 3, bit = t & 7;
-        uint32_t P = 0;
-        for (int j = 0; j < FPL; ++j) {
-            const int f = h * FPL + j;
-            const bool v = f < F && ((live >> f) & 1u);
-            const int sl = v ? A.fmax[f] - A.sel0[f] : 255;
-            P |= (uint32_t)((sl >> bit) & 1) << j;
-        }
-        mnx_s[t] = (int32_t)P;
-    }
-    for (int t = threadIdx.x; t < WN; t += blockDim.x) {
-        pres0_s[t] = t < W ? A.present0[t] : 0ull;
-        pres0_rev[t] = WN - 1 - t < W ? __brevll(A.present0[WN - 1 - t]) : 0ull;
-    }
-    __syncthreads();
+    // everything below slot_all is the instance's image (draw_image_build): dead features (min = max = 0)
+    // removed from the rows and the person masks, the start keys packed, the slack planes sliced
+    // (mnx_s[8 glane + i] bit j = bit i of the slack of feature glane * FPL + j; dead and padding
+    // features all ones, never picked, so never 0), the start pool also mirrored
+    load_draw_image(smem, A.image, L.words / 2);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int glane = lane & 1, gbase = lane & ~1;

@@ -52,52 +52,21 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
     constexpr bool kSlackPlanes = FN >= 16;
     static_assert(FN <= 32 && WN <= 32 && (FN % 8) == 0 && (WN % 2) == 0 && NP >= 1 && NP <= 8, "solo draw layout");
     extern __shared__ uint64_t smem[];
-    const int F = A.F, W = A.W, n = A.n, k = A.k;
+    const int n = A.n, k = A.k;
+    const DrawImage L = draw_image_layout(false, FN, WN, n);
     uint64_t *fm = smem;
-    uint32_t *pm = reinterpret_cast<uint32_t *>(fm + FN * LS);
-    int32_t *need0_s = reinterpret_cast<int32_t *>(pm + ((n + 3) & ~3));
+    uint32_t *pm = reinterpret_cast<uint32_t *>(fm + L.pm);
+    int32_t *need0_s = reinterpret_cast<int32_t *>(fm + L.need0);
     int32_t *rem0_s = need0_s + FN, *mnx_s = need0_s + 2 * FN;
-    uint64_t *pres0_s = reinterpret_cast<uint64_t *>(need0_s + 4 * FN);
-    uint64_t *slot_all = pres0_s + WN;
+    uint64_t *pres0_s = fm + L.pres0;
+    uint64_t *slot_all = fm + L.words;
     int32_t *cnt_all = reinterpret_cast<int32_t *>(slot_all + (kSoloThreads / 64) * kSoloSlots * WN);
 
-    uint32_t live = 0;  // features with max > 0 (dead min = max = 0 features are removed)
-    for (int f = 0; f < F; ++f) live |= (uint32_t)(A.fmax[f] != 0) << f;
-    for (int t = threadIdx.x; t < FN * LS; t += blockDim.x) {
-        const int f = t / LS, w = t - f * LS;
-        const bool lf = f < F && ((live >> f) & 1u);
-        fm[t] = (lf && w < W) ? A.featmask[f * A.Ws + w] : 0ull;
-    }
-    for (int t = threadIdx.x; t < n; t += blockDim.x) pm[t] = A.pmask[t] & live;
-    for (int t = threadIdx.x; t < FN; t += blockDim.x) {
-        const bool v = t < F && ((live >> t) & 1u);
-        if constexpr (K8) {  // 8-bit need keys carrying their index (draw_lane.inc, K8)
-            need0_s[t] = k8pack(v ? A.fmin[t] - A.sel0[t] : 0, v ? A.rem0[t] : 0, t);
-        } else {
-            need0_s[t] = v ? A.fmin[t] - A.sel0[t] : 0;
-            rem0_s[t] = v ? A.rem0[t] : 0;
-        }
-    }
-    // FN >= 16: slack = max - selected of every feature, bit-sliced: mnx_s[i] bit j = bit i of the
-    // slack of feature j, planes 0..NP-1 kept (dead and padding features all ones, never picked);
-    // FN = 8: mnx_s[f] = min - max + 1
-    if constexpr (!kSlackPlanes) {
-        for (int t = threadIdx.x; t < FN; t += blockDim.x) {
-            const bool v = t < F && ((live >> t) & 1u);
-            mnx_s[t] = v ? A.fmin[t] - A.fmax[t] + 1 : -(1 << 30);
-        }
-    }
-    for (int t = threadIdx.x; kSlackPlanes && t < 8; t += blockDim.x) {
-        uint32_t P = 0;
-        for (int j = 0; j < FN; ++j) {
-            const bool v = j < F && ((live >> j) & 1u);
-            const int sl = v ? A.fmax[j] - A.sel0[j] : 255;
-            P |= (uint32_t)((sl >> t) & 1) << j;
-        }
-        mnx_s[t] = (int32_t)P;
-    }
-    for (int t = threadIdx.x; t < WN; t += blockDim.x) pres0_s[t] = t < W ? A.present0[t] : 0ull;
-    __syncthreads();
+    // everything below slot_all is the instance's image (draw_image_build, as draw_lane_kernel): dead
+    // features removed, the start keys packed, and mnx_s the slack of every feature, bit-sliced (FN >= 16:
+    // mnx_s[i] bit j = bit i of the slack of feature j, dead and padding features all ones), or
+    // mnx_s[f] = min - max + 1 (FN = 8)
+    load_draw_image(smem, A.image, L.words / 2);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint64_t *slots = slot_all + (size_t)wave * kSoloSlots * WN;
