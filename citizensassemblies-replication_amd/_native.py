@@ -66,6 +66,7 @@ SIGNATURES = {
     "csa_picks_pack_async": (ctypes.c_int, [_P, _U64, _I32, _I32, _P, _P, _P]),
     "csa_panel_hash_async": (ctypes.c_int, [_P, _U64, _I32, _P, _P]),
     "csa_draw_kernel_name": (ctypes.c_int, [_P, _I32, ctypes.c_char_p, _U64]),
+    "csa_draw_kernel_list": (ctypes.c_int, [ctypes.c_char_p, _U64]),
     "csa_xt_pad": (_I32, [_I32]),
     "csa_transpose_count_async": (ctypes.c_int, [_P, _U64, _I32, _P, _P, _P]),
     "csa_pair_scratch_bytes": (_U64, [_I32, _U64, _U32]),
@@ -148,6 +149,13 @@ def check(rc):
     if rc != CSA_OK:
         raise CsaError(rc, last_error())
     return rc
+
+
+def draw_kernel_list():
+    """Names of every draw-kernel instantiation the library can launch (csa_draw_kernel_list; no device)."""
+    buf = ctypes.create_string_buffer(1 << 14)
+    check(lib().csa_draw_kernel_list(buf, len(buf)))
+    return buf.value.decode().splitlines()
 
 
 def ptr(a):

@@ -2057,6 +2057,20 @@ int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
     return CSA_OK;
 }
 
+// The instantiation a DrawConfig stands for, spelled as the profiler prints it (csa_draw_kernel_name,
+// csa_draw_kernel_list).  `general`: draw_kernel's GENERAL parameter.
+void draw_config_name(const DrawConfig &c, bool general, char *buf, size_t len) {
+    if (c.solo)
+        snprintf(buf, len, "draw_solo_kernel<%d, %d, %d, %s>", c.FPL, c.WPL, c.np, c.k8 ? "true" : "false");
+    else if (c.lane)
+        snprintf(buf, len, "draw_lane_kernel<%d, %d, %d, %d, %s>", c.FPL, c.WPL,
+                 (c.WPL / 2 + CSA_LANE_SKDIV - 1) / CSA_LANE_SKDIV, c.np, c.k8 ? "true" : "false");
+    else if (c.wide)
+        snprintf(buf, len, "draw_wide_kernel<%d, %d, %d>", c.G, c.FPL, c.WPL);
+    else
+        snprintf(buf, len, "draw_kernel<%d, %d, %d, %s>", c.G, c.FPL, c.WPL, general ? "true" : "false");
+}
+
 // The register kernels' attempt-start tables, built on the host from the instance and its start state
 // (I->sel0, I->rem0h, I->present0h, I->need8) and uploaded as one image in the kernels' LDS layout
 // (draw_image_layout, draw_lane.inc): called when the instance is created and whenever
@@ -2904,15 +2918,43 @@ int csa_draw_kernel_name(const csa_instance *I, int32_t k, char *buf, uint64_t l
     DrawConfig cfg;
     rc = pick_draw_config(I, false, cfg);
     if (rc) return rc;
-    if (cfg.solo)
-        snprintf(buf, (size_t)len, "draw_solo_kernel<%d, %d, %d, %s>", cfg.FPL, cfg.WPL, cfg.np, cfg.k8 ? "true" : "false");
-    else if (cfg.lane)
-        snprintf(buf, (size_t)len, "draw_lane_kernel<%d, %d, %d, %d, %s>", cfg.FPL, cfg.WPL,
-                 (cfg.WPL / 2 + CSA_LANE_SKDIV - 1) / CSA_LANE_SKDIV, cfg.np, cfg.k8 ? "true" : "false");
-    else if (cfg.wide)
-        snprintf(buf, (size_t)len, "draw_wide_kernel<%d, %d, %d>", cfg.G, cfg.FPL, cfg.WPL);
-    else
-        snprintf(buf, (size_t)len, "draw_kernel<%d, %d, %d, false>", cfg.G, cfg.FPL, cfg.WPL);
+    draw_config_name(cfg, false, buf, (size_t)len);
+    return CSA_OK;
+}
+
+// Every instantiation pick_draw_config can resolve, asked of the dispatch functions themselves: the
+// candidate ranges are wider than anything built, and a combination counts when its dispatcher
+// returns a kernel (solo at FN < 16 takes no plane count: pick_draw_config reports np = 8 there).
+int csa_draw_kernel_list(char *buf, uint64_t len) {
+    std::string all;
+    char name[128];
+    // choice: pick_draw_config's (1 solo, 2 lane, 8 wide, 16 / 64 draw_kernel)
+    auto add = [&](const void *fn, int choice, int fpl, int wpl, int np, bool k8, bool general) {
+        if (!fn) return;
+        DrawConfig c;
+        c.G = choice, c.FPL = fpl, c.WPL = wpl, c.np = np, c.k8 = k8;
+        c.solo = choice == 1, c.lane = choice == 2, c.wide = choice == 8;
+        draw_config_name(c, general, name, sizeof name);
+        all += name;
+        all += '\n';
+    };
+    for (int fn = 1; fn <= 64; ++fn)
+        for (int wn = 1; wn <= 64; ++wn)
+            for (int np = 1; np <= 8; ++np)
+                for (int k8 = 1; k8 >= 0; --k8) {
+                    if (fn >= 16 || np == 8) add(solo_fn(fn, wn, k8 != 0, np), 1, fn, wn, np, k8 != 0, false);
+                    add(lane_fn(fn, wn, k8 != 0, np), 2, fn, wn, np, k8 != 0, false);
+                }
+    for (int fpl = 1; fpl <= 16; ++fpl)
+        for (int wpl = 1; wpl <= 32; ++wpl) {
+            add(wide_fn(fpl, wpl), 8, fpl, wpl, 8, false, false);
+            add(draw_fn_fw<16, false>(fpl, wpl), 16, fpl, wpl, 8, false, false);
+            add(draw_fn_fw<64, false>(fpl, wpl), 64, fpl, wpl, 8, false, false);
+            add(draw_fn_fw<64, true>(fpl, wpl), 64, fpl, wpl, 8, false, true);
+        }
+    if (!buf || len < all.size() + 1)
+        return fail(CSA_E_INVALID, "draw kernel list: the buffer needs %zu bytes", all.size() + 1);
+    memcpy(buf, all.c_str(), all.size() + 1);
     return CSA_OK;
 }
 

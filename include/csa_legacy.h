@@ -40,7 +40,7 @@ extern "C" {
 #define CSA_E_BAD_QUOTAS 2     /* sum(min) <= k <= sum(max) violated: analysis.py:174-176 assert */
 #define CSA_E_NO_CANDIDATE 3   /* no candidate feature: the reference's KeyError, legacy.py:188  */
 #define CSA_E_ATTEMPT_LIMIT 4  /* new: the reference restarts forever (analysis.py:146)          */
-#define CSA_E_UNSUPPORTED 5    /* instance exceeds the kernels' limits (F > 64, n > 16384, ...)  */
+#define CSA_E_UNSUPPORTED 5    /* instance exceeds the kernels' limits (F > 256, n > 16384, ...) */
 #define CSA_E_HIP 6            /* HIP runtime / device error                                     */
 #define CSA_E_SELECTION 7      /* one attempt raised SelectionError (legacy.py:34-36)            */
 
@@ -260,6 +260,12 @@ int csa_panel_hash_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W,
 /* Name of the draw kernel csa_draw_async launches for this instance and k
  * (e.g. "draw_lane_kernel<32, 28, 14, 7, true>"), for matching profiler output. */
 int csa_draw_kernel_name(const csa_instance *inst, int32_t k, char *buf, uint64_t len);
+
+/* Names of every draw-kernel instantiation the dispatcher can resolve (batch draws and the GENERAL
+ * kernels of csa_legacy_find / single attempts / index-list re-draws), newline-separated, spelled as
+ * csa_draw_kernel_name spells them and taken from the dispatch tables themselves.  Needs no device.
+ * CSA_E_INVALID when buf is NULL or len is too small; csa_last_error then names the size needed. */
+int csa_draw_kernel_list(char *buf, uint64_t len);
 
 /* Bit-transpose + per-person count.  Panels (n_panels*W) -> d_xt, the
  * panel-indicator matrix transposed and packed in two 32-bit planes per
