@@ -557,10 +557,18 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                 for (int j = 0; j < WPL; ++j) rw[j] = row[j];
                 // the scan runs over word PAIRS: the pair whose preceding holder count is < rr is
                 // kept (both masked words, the count before it), then one compare picks the word
-                // inside it -- the count / index selects once per two words (7.5 VALU per word
-                // instead of 9)
+                // inside it.  Every pair forms its masked words and counts them for all lanes (the
+                // count chain never waits on a predicate); the keep is four moves under the pair's
+                // own lane predicate `acc < rr` -- v_mov_b32 for the count and the index, one
+                // v_mov_b64 per masked word -- instead of six v_cndmask.  The scheduling barrier (no
+                // instruction) keeps the body from being turned back into selects.
                 // (rr >= 1 on both lanes, so the first pair is always taken: it initialises the kept
-                // pair and the select chain starts at the second)
+                // pair and the predicated keeps start at the second)
+                // (`acc < rr` is monotone, and draw_solo_kernel nests the pairs under a narrowing
+                // predicate, a lane leaving the scan at the first pair it does not take; here, with
+                // seven pairs and one lane of each pair scanning to the end, the nested form put the
+                // compare -> exec -> count chain in series and measured 1.1 % slower at sf_e:
+                // DESIGN 4.1)
                 int base = 0, wsp = 0;
                 uint64_t ma = rm[0] & rw[0], mb = rm[1] & rw[1];
                 int acc = bcnt_acc((uint32_t)(ma >> 32), bcnt_acc((uint32_t)ma, 0));
@@ -568,11 +576,21 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
 #pragma unroll
                 for (int j = 2; j < WPL; j += 2) {
                     const uint64_t m0 = rm[j] & rw[j], m1 = rm[j + 1] & rw[j + 1];
-                    const bool tk = acc < rr;
-                    base = tk ? acc : base;
-                    wsp = tk ? j : wsp;
-                    ma = tk ? m0 : ma;
-                    mb = tk ? m1 : mb;
+                    if constexpr (WN < 32) {
+                        if (acc < rr) {
+                            base = acc;
+                            wsp = j;
+                            ma = m0;
+                            mb = m1;
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    } else {  // WN = 32 has no register to spare: the predicated form spills there
+                        const bool tk = acc < rr;
+                        base = tk ? acc : base;
+                        wsp = tk ? j : wsp;
+                        ma = tk ? m0 : ma;
+                        mb = tk ? m1 : mb;
+                    }
                     acc = bcnt_acc((uint32_t)(m0 >> 32), bcnt_acc((uint32_t)m0, acc));
                     acc = bcnt_acc((uint32_t)(m1 >> 32), bcnt_acc((uint32_t)m1, acc));
                 }
@@ -613,19 +631,26 @@ __global__ __launch_bounds__(kLaneThreads, CSA_LANE_OCC) void draw_lane_kernel(D
                     fl = (picked & ~nz) << fbase;
                 }
                 LANE_REGION(update, 0, false);  // (runs with `pick`)
-                // drop the pick from the register pool without a branch: the one-hot word mask
-                // (0 on the other lane) sign-extends to -1 for word ws only (one bfe per word), and
-                // both dwords clear the pick's bit with one v_bitop3 each (rm & ~(bit & sel)):
-                // 3 VALU per word (round 2's bfe + shift-add per dword: 4)
+                // drop the pick from the register pool: the picked bit is set in rm[ws] (it was taken
+                // from rm[ws] & row[ws]), so clearing it is subtracting it -- one 64-bit add of -(1 << b)
+                // = ~0 << b.  Each lane forms the addends of a pair's two words once (the other word's
+                // is 0) and each pair adds them under its own lane predicate (the hit lane whose kept
+                // pair it is): a compare and two v_lshl_add_u64 per pair instead of a bfe + two
+                // v_bitop3 per word.  The non-hit lane matches no pair and leaves its pool untouched.
+                // The scheduling barrier (no instruction) keeps the body from being turned into
+                // selects; unlike an empty asm it leaves the compiler free to drop the skip branch
+                // around the two adds.
                 {
-                    const uint32_t M = hit ? 1u << ws : 0u;
-                    const uint32_t bit = 1u << ((uint32_t)b & 31u), Blo = b < 32 ? bit : 0u, Bhi = b < 32 ? 0u : bit;
+                    const uint64_t nb = ~0ull << b;
+                    const uint64_t dA = second ? 0ull : nb, dB = second ? nb : 0ull;
+                    const int wh = hit ? wsp : -1;
 #pragma unroll
-                    for (int j = 0; j < WPL; ++j) {
-                        const uint32_t sel = (uint32_t)((int)(M << (31 - j)) >> 31);
-                        const uint32_t lo = (uint32_t)rm[j] & ~(Blo & sel);
-                        const uint32_t hi = (uint32_t)(rm[j] >> 32) & ~(Bhi & sel);
-                        rm[j] = ((uint64_t)hi << 32) | lo;
+                    for (int j = 0; j < WPL; j += 2) {
+                        if (wh == j) {
+                            rm[j] += dA;
+                            rm[j + 1] += dB;
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
                     }
                 }
                 // the pick of step s joins its 8-step chunk (lane 0: slots 0-3, lane 1: slots 4-7);

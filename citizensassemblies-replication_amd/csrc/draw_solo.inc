@@ -177,7 +177,19 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                 const int r = 1 + (int)__umulhi(word, (uint32_t)bd);  // randint(1, rem[f*]), legacy.py:149
                 const uint64_t *row = (K8 ? fm - LS : fm) + bi * LS;
                 // forward scan over word pairs: the pair whose preceding holder count is < r is kept
-                // (both masked words and the count before it); row reads in batches of RB words
+                // (both masked words and the count before it); row reads in batches of RB words.
+                // `acc < r` is monotone, so the keep runs under a narrowing lane predicate instead of
+                // selects (draw_lane.inc): a lane leaves the scan at the first pair it does not take --
+                // its r-th holder is in the pair it kept -- and under the predicate the masked words are
+                // formed in place (the empty asm keeps the body from being turned back into selects).
+                // Both guards -- this asm and the drop's scheduling barrier -- stop the compiler's
+                // if-conversion and nothing else; after a compiler update, tools/kernel_regs.sh and the
+                // v_cndmask / v_bitop3 count of the step loop's ISA say whether they still do (a failure
+                // is slower, not wrong).
+                // kPredicated: <16, 28, 5, true> is the one FN = 16 form that fits 4 waves per SIMD
+                // (128 VGPRs; the launch bounds ask for 3) and either predicated block costs it that
+                // wave (139 / 129 VGPRs), so it keeps the selects and the v_bitop3 drop.
+                constexpr bool kPredicated = !(FN == 16 && WN == 28 && NP == 5 && K8);
                 int acc = 0, base = 0, wsp = 0;
                 uint64_t ma = 0ull, mb = 0ull;
                 constexpr int RB = 4;  // 4-word row batches: FN = 8 fits 128 VGPRs without spills (8: a few, -0.9 %)
@@ -189,16 +201,28 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
 #pragma unroll
                     for (int u = 0; u < RB && j0 + u < WN; u += 2) {
                         const int j = j0 + u;
-                        const uint64_t m0 = rm[j] & rw[u], m1 = rm[j + 1] & rw[u + 1];
-                        const bool tk = acc < r;
-                        base = tk ? acc : base;
-                        wsp = tk ? j : wsp;
-                        ma = tk ? m0 : ma;
-                        mb = tk ? m1 : mb;
-                        acc = bcnt_acc((uint32_t)(m0 >> 32), bcnt_acc((uint32_t)m0, acc));
-                        acc = bcnt_acc((uint32_t)(m1 >> 32), bcnt_acc((uint32_t)m1, acc));
+                        if constexpr (kPredicated) {
+                            if (j > 0 && !(acc < r)) goto scanned;  // (r >= 1: the first pair is always taken)
+                            base = acc;
+                            wsp = j;
+                            ma = rm[j] & rw[u];
+                            mb = rm[j + 1] & rw[u + 1];
+                            asm("" : "+v"(ma), "+v"(mb));
+                            acc = bcnt_acc((uint32_t)(ma >> 32), bcnt_acc((uint32_t)ma, acc));
+                            acc = bcnt_acc((uint32_t)(mb >> 32), bcnt_acc((uint32_t)mb, acc));
+                        } else {
+                            const uint64_t m0 = rm[j] & rw[u], m1 = rm[j + 1] & rw[u + 1];
+                            const bool tk = acc < r;
+                            base = tk ? acc : base;
+                            wsp = tk ? j : wsp;
+                            ma = tk ? m0 : ma;
+                            mb = tk ? m1 : mb;
+                            acc = bcnt_acc((uint32_t)(m0 >> 32), bcnt_acc((uint32_t)m0, acc));
+                            acc = bcnt_acc((uint32_t)(m1 >> 32), bcnt_acc((uint32_t)m1, acc));
+                        }
                     }
                 }
+            [[maybe_unused]] scanned:
                 const int c0 = __popcll(ma);
                 const bool second = r - base > c0;  // the holder is in the pair's second word
                 const uint64_t ms = second ? mb : ma;
@@ -206,9 +230,23 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                 const int b = select_bit(ms, r - base - (second ? c0 : 0));
                 const int p = ws * 64 + b;
                 const uint32_t hb = pm[p];
-                // drop the pick from the register pool (one bfe + two v_bitop3 per word) while the
-                // pm[p] read is in flight: none of it needs the pick's features
-                {
+                // drop the pick from the register pool while the pm[p] read is in flight (none of it
+                // needs the pick's features): the picked bit is set in rm[ws], so clearing it is adding
+                // -(1 << b) = ~0 << b; the addends of a pair's two words are formed once (the other
+                // word's is 0) and each pair adds them under its own lane predicate -- a compare and
+                // two v_lshl_add_u64 per pair instead of a bfe + two v_bitop3 per word (draw_lane.inc)
+                if constexpr (kPredicated) {
+                    const uint64_t nb = ~0ull << b;
+                    const uint64_t dA = second ? 0ull : nb, dB = second ? nb : 0ull;
+#pragma unroll
+                    for (int j = 0; j < WN; j += 2) {
+                        if (wsp == j) {
+                            rm[j] += dA;
+                            rm[j + 1] += dB;
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                } else {  // branch-free: one bfe (the word's select mask) + one v_bitop3 per dword
                     const uint32_t M = 1u << ws;
                     const uint32_t bit = 1u << ((uint32_t)b & 31u), Blo = b < 32 ? bit : 0u, Bhi = b < 32 ? 0u : bit;
 #pragma unroll

@@ -146,6 +146,49 @@ KERNEL_U32(k_mul24sdwa, OPMUL)
 KERNEL_U32(k_mad24, OPMAD24)
 KERNEL_U32(k_pk_add_u16, OPPKADD16)
 
+// 64-bit forms (register pairs) and a move under a partial exec mask: what the draw kernels' predicated
+// holder-scan keep (v_mov_b64 / v_mov_b32 under the lane predicate) and pool drop (v_lshl_add_u64) issue.
+// PRED: 0 = every lane, else the lanes with (lane & PRED) != 0 run the chains (the compiler masks exec
+// around the loop; nothing here writes exec).
+#define KERNEL_U64(NAME, OP, PRED)                                                      \
+    __global__ __launch_bounds__(256) void NAME(uint32_t *out, uint32_t s) {            \
+        uint64_t v[8];                                                                  \
+        const uint64_t ss = ((uint64_t)s << 32) | threadIdx.x;                          \
+        for (int c = 0; c < 8; ++c) v[c] = threadIdx.x + c;                             \
+        if (PRED == 0 || (threadIdx.x & PRED)) {                                        \
+            CHAINS(OP)                                                                  \
+        }                                                                               \
+        uint64_t r = 0;                                                                 \
+        for (int c = 0; c < 8; ++c) r ^= v[c];                                          \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = (uint32_t)r ^ (uint32_t)(r >> 32); \
+    }
+#define OPMOVB64(x) asm volatile("v_mov_b64 %0, %1" : "+v"(x) : "v"(ss))
+#define OPLSHLADD64(x) asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(x) : "v"(ss))
+KERNEL_U64(k_mov_b64, OPMOVB64, 0)
+KERNEL_U64(k_mov_b64_half, OPMOVB64, 1)
+KERNEL_U64(k_lshl_add_u64, OPLSHLADD64, 0)
+KERNEL_U64(k_lshl_add_u64_half, OPLSHLADD64, 1)
+__global__ __launch_bounds__(256) void k_mov32_half(uint32_t *out, uint32_t s) {
+    uint32_t v[8];
+    for (int c = 0; c < 8; ++c) v[c] = threadIdx.x + c;
+    if (threadIdx.x & 1) {
+        CHAINS(OPMOV32)
+    }
+    uint32_t r = 0;
+    for (int c = 0; c < 8; ++c) r ^= v[c];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = r;
+}
+__global__ __launch_bounds__(256) void k_mov32_one(uint32_t *out, uint32_t s) {
+    uint32_t v[8];
+    for (int c = 0; c < 8; ++c) v[c] = threadIdx.x + c;
+    if ((threadIdx.x & 63) == 5) {
+        CHAINS(OPMOV32)
+    }
+    uint32_t r = 0;
+    for (int c = 0; c < 8; ++c) r ^= v[c];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = r;
+}
+
 __global__ __launch_bounds__(256) void k_fma(float *out, float s) {
     float v[8];
     for (int c = 0; c < 8; ++c) v[c] = threadIdx.x + c;
@@ -271,6 +314,12 @@ int main(int argc, char **argv) {
             run("v_add_u32_dpp", k_dpp, d, 3u, w, 1);
             run("v_mul_f32", k_mul_f32, f, 1.0001f, w, 1);
             run("v_fma_f32", k_fma, f, 1.0001f, w, 1);
+            run("v_mov_b64", k_mov_b64, d, 3u, w, 1);
+            run("v_mov_b64 exec = odd lanes", k_mov_b64_half, d, 3u, w, 1);
+            run("v_lshl_add_u64", k_lshl_add_u64, d, 3u, w, 1);
+            run("v_lshl_add_u64 exec = odd lanes", k_lshl_add_u64_half, d, 3u, w, 1);
+            run("v_mov_b32_e32 exec = odd lanes", k_mov32_half, d, 3u, w, 1);
+            run("v_mov_b32_e32 exec = one lane", k_mov32_one, d, 3u, w, 1);
         }
         hipFree(d);
         hipFree(f);
