@@ -11,14 +11,20 @@ reference's legacy.py / analysis.py LEGACY functions:
 plus set_rng_mode("mt" | "philox") (the reference's own MT19937 stream on the host, or the
 device's Philox verification-mode stream, the default)
 
+plus the analysis side of LEXIMIN / XMIN after the solver (analysis.py:194-228):
+leximin_probabilities, xmin_probabilities (solver passed in or imported from the reference)
+and portfolio_probabilities, bit-equal float64 sums in portfolio order on the device
+
 plus xmin._get_panel_not_in_portfolio_if_possible (XMIN's LEGACY caller,
 xmin.py:464-474) on the device.
 """
 from .instance import Instance, read_instance, encode  # noqa: F401
 from .legacy import SelectionError, check_min_cats, find_random_sample_legacy, seed, set_rng_mode  # noqa: F401
 from .analysis import PairHistogram, PanelSet, legacy_find, legacy_find_batch, legacy_probabilities  # noqa: F401
+from .analysis import leximin_probabilities, portfolio_probabilities, xmin_probabilities  # noqa: F401
 from . import _native, xmin  # noqa: F401
 
 __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_cats",
            "find_random_sample_legacy", "seed", "set_rng_mode", "PairHistogram", "PanelSet", "legacy_find",
-           "legacy_find_batch", "legacy_probabilities"]
+           "legacy_find_batch", "legacy_probabilities", "leximin_probabilities", "xmin_probabilities",
+           "portfolio_probabilities"]

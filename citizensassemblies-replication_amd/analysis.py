@@ -13,7 +13,15 @@ Kept names and semantics (reference file:line):
                                        MFMA (exact 0/1 products, f32 accumulation; int8
                                        selectable), exact distinct-panel count; returns
                                        ``(alloc, found_panels, pair_histogram)``.
-LEXIMIN / XMIN and the plotting / statistics code stay in the reference (CPU).
+  * ``leximin_probabilities``,         analysis.py:194-228 -- the solver itself stays a host callable
+    ``xmin_probabilities``             (``find_distribution=``, or the reference's module when
+                                       importable); what follows it -- selection_probs, the pair
+                                       histogram, the panel set -- is ``portfolio_probabilities``:
+                                       one upload of the packed panels and the weights, the bit
+                                       transpose, and portfolio_pairs_kernel, which sums every
+                                       pair's and person's probabilities in portfolio order in
+                                       float64, so the values are the reference's bit for bit.
+The LEXIMIN / XMIN solvers (Gurobi) and the plotting code stay in the reference (CPU).
 """
 import ctypes
 import os
@@ -57,7 +65,12 @@ class PairHistogram:
     ``_u`` on first access: the triangle is packed and divided on the device
     (csa_pairs_upper_async) and only its n(n-1)/2 float64 values cross PCIe, so a caller
     that only reads per-person probabilities or ``len(found_panels)`` never moves it.
+    A histogram built by ``portfolio_probabilities`` (LEXIMIN / XMIN) keeps the device's packed
+    float64 triangle (``_dtri``) the same way: copied on first access, sorted on the device by
+    ``stats.sorted_pair_probabilities``.  Pickles hold host data only.
     """
+
+    _dtri = None    # device float64 triangle (portfolio_pairs_kernel's output), copied on first access
 
     def __init__(self, number_of_agents, uniform_distribution=False, counts=None):
         n = int(number_of_agents)
@@ -108,10 +121,34 @@ class PairHistogram:
             u = _divide(u, dv)
         return u
 
+    @classmethod
+    def _from_device_triangle(cls, n, tri):
+        """Histogram over a device float64 triangle (n(n-1)/2 values, at least one element allocated)."""
+        h = cls(n)
+        h._uv, h._dtri = None, tri
+        return h
+
+    def _materialise_triangle(self):
+        """One copy of the device float64 triangle into pinned host memory; pending divisions follow."""
+        import torch
+        tri, m = self._dtri, self.n * (self.n - 1) // 2
+        with torch.cuda.device(tri.device):
+            st = torch.cuda.current_stream(tri.device)
+            h = torch.empty(max(m, 1), dtype=torch.float64, pin_memory=True)
+            h.copy_(tri[:max(m, 1)], non_blocking=True)
+            st.synchronize()
+        u = h.numpy()[:m]
+        for dv in self._divs:
+            u = _divide(u, dv)
+        return u
+
     @property
     def _u(self):
         if self._uv is None:
-            if isinstance(self._src, np.ndarray):
+            if self._dtri is not None:
+                u = self._materialise_triangle()
+                self._dtri = None
+            elif isinstance(self._src, np.ndarray):
                 u = self._src[np.triu_indices(self.n, 1)]
                 for d in self._divs:
                     u = _divide(u, d)
@@ -122,7 +159,7 @@ class PairHistogram:
 
     @_u.setter
     def _u(self, value):
-        self._uv, self._src, self._divs = value, None, []
+        self._uv, self._src, self._divs, self._dtri = value, None, [], None
 
     def _index(self, i, j):
         return i * (self.n - 1) - i * (i - 1) // 2 + (j - i - 1)
@@ -163,13 +200,39 @@ class PairHistogram:
             self._u = _divide(self._uv, num)
         self._counts = self._S = None
 
-    def add_portfolio_of_panels_to_histogram(self, portfolio, probabilities):
+    def add_portfolio_of_panels_to_histogram(self, portfolio, probabilities, device=None):
+        """analysis.py:90-95.  By default on the host, one ``np.add.at`` per panel.  ``device=True``
+        adds float probabilities with portfolio_pairs_kernel onto the current values (the same
+        float64 sums in the same order, so the same bits; the triangle then stays on the device
+        until it is read).  Integer weights always take the host path, so counts stay ints."""
         self._counts = self._S = None
+        if device:
+            pairs = list(zip(portfolio, probabilities))
+            if pairs and all(isinstance(pob, float) for _, pob in pairs):
+                return self._add_portfolio_device(pairs)
+            portfolio, probabilities = [p for p, _ in pairs], [w for _, w in pairs]
         for panel, pob in zip(portfolio, probabilities):
             idx = np.asarray(sorted(panel), np.int64)
             u = self._writable(isinstance(pob, float))
             ii, jj = np.triu_indices(len(idx), 1)
             np.add.at(u, self._index(idx[ii], idx[jj]), pob)
+
+    def _add_portfolio_device(self, pairs):
+        """``pairs``: (panel, float probability) in portfolio order; panels name agents 0..n-1, the
+        histogram's keys.  The current values go to the device (or are there already) and
+        portfolio_pairs_kernel adds onto them (CSA_PORTFOLIO_ACCUMULATE)."""
+        import torch
+        n = self.n
+        rows = _pack_positions([panel for panel, _ in pairs], n)     # KeyError: a key outside 0..n-1
+        weights = np.array([pob for _, pob in pairs], np.float64)
+        m = n * (n - 1) // 2
+        if self._dtri is not None and not self._divs and self._uv is None:
+            tri = self._dtri
+        else:
+            tri = torch.from_numpy(np.ascontiguousarray(self._writable(True))).to("cuda") if m else \
+                torch.zeros(1, dtype=torch.float64, device="cuda")
+        _portfolio_launch(rows, weights, n, tri, None, accumulate=True)
+        self._uv, self._src, self._divs, self._dtri = None, None, [], tri
 
     def upper(self):
         """Values of all pairs i < j in the reference's key order (row-major); read-only."""
@@ -598,3 +661,136 @@ def finish(instance, enc, raw, S):
     hist._counts, hist._S = raw.pairs, S      # integer counts for stats.sorted_pair_probabilities
     panels = PanelSet(raw.unique, raw.panels, enc.n, enc.agent_ids)
     return alloc, panels, hist
+
+
+# ---- LEXIMIN / XMIN: everything after the solver (analysis.py:194-228) ----------------------------
+
+def _membership(panels, n, lookup=None):
+    """Panels (sized iterables of agent positions 0..n-1, or of keys that ``lookup`` turns into
+    positions) -> (x, rows): the P x 64W boolean membership matrix and its uint64[P, W] bitmask rows
+    (``xmin.pack_portfolio``'s rows).  One C-level pass over the members; a position outside 0..n-1
+    raises KeyError, a panel that names an agent twice ValueError (a bitmask cannot hold it)."""
+    from itertools import chain
+    W = max((n + 63) // 64, 1)
+    panels = [p if hasattr(p, "__len__") else tuple(p) for p in panels]
+    P = len(panels)
+    lens = np.fromiter(map(len, panels), np.int64, P)
+    members = chain.from_iterable(panels)
+    flat = np.fromiter(map(lookup, members) if lookup else members, np.int64, int(lens.sum()))
+    bad = flat[(flat < 0) | (flat >= n)]
+    if bad.size:
+        raise KeyError(int(bad[0]))
+    x = np.zeros((P, W * 64), np.bool_)
+    x[np.repeat(np.arange(P), lens), flat] = True
+    if int(np.count_nonzero(x)) != len(flat):
+        raise ValueError("a panel of the portfolio names an agent more than once")
+    return x, np.ascontiguousarray(np.packbits(x, axis=1, bitorder="little")).view("<u8").reshape(P, W)
+
+
+def _pack_positions(idx, n):
+    """Panels as lists of agent positions (0..n-1) -> uint64[P, W] bitmask rows."""
+    return _membership(idx, n)[1]
+
+
+def _portfolio_launch(rows, weights, n, d_upper, d_alloc, accumulate=False):
+    """Upload the packed rows and the weights, transpose (csa_transpose_count_async) and run
+    portfolio_pairs_kernel into ``d_upper`` / ``d_alloc`` (device float64 tensors or None), all on the
+    outputs' device and its current stream.  Nothing waits for the kernels: the caller reads what it
+    needs."""
+    import torch
+    L = N.lib()
+    P = len(weights) if n else 0
+    dev = (d_upper if d_upper is not None else d_alloc).device
+    with torch.cuda.device(dev):
+        sp = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        xt = w = None
+        if P:
+            d_rows = torch.from_numpy(rows.view(np.int64).reshape(-1)).to(dev)
+            w = torch.from_numpy(np.ascontiguousarray(weights, np.float64)).to(dev)
+            xt = torch.empty(((P + 63) // 64) * L.csa_xt_pad(n), dtype=torch.int64, device=dev)
+            cnt = torch.zeros(n, dtype=torch.int64, device=dev)     # the transpose's counts: not used
+            N.check(L.csa_transpose_count_async(N.ptr(d_rows), P, n, N.ptr(xt), N.ptr(cnt), sp))
+        N.check(L.csa_portfolio_pairs_async(N.ptr(xt), P, n, N.ptr(w), N.ptr(d_upper), N.ptr(d_alloc),
+                                            N.CSA_PORTFOLIO_ACCUMULATE if accumulate else 0, sp))
+
+
+def portfolio_probabilities(instance: Instance, portfolio, probabilities, min_probability=None):
+    """What the reference's leximin_probabilities / xmin_probabilities compute from the solver's
+    ``(portfolio, probabilities)`` (analysis.py:204-210, 222-228), on the device.
+
+    Returns ``(alloc, panels, pair_histogram)``:
+
+    * ``alloc``: ``{agent_id: float}`` over all agents in instance order, each the sum of the
+      probabilities of the panels holding the agent, added in portfolio order from ``0.``;
+    * ``panels``: the ``set`` of panels as tuples of agent ids -- all of them, or with
+      ``min_probability`` those whose probability is ``> min_probability`` (analysis.py:209 uses
+      ``1e-11``).  The reference's tuples are in frozenset iteration order; ours are sorted by the
+      agents' position in the instance;
+    * ``pair_histogram``: every pair's sum of panel probabilities in portfolio order
+      (analysis.py:90-95), kept on the device until read.
+
+    Portfolio and probabilities are paired with ``zip`` (the shorter one ends both), as the
+    reference does.  An agent id that is not in the instance raises ``KeyError``, as
+    ``selection_probs[agent_id] +=`` does there.  Only the packed panels and the weights are
+    uploaded; only ``alloc`` and, on first access, the triangle are read back.  Both results are the
+    reference's float64 values bit for bit (csa_portfolio_pairs_async's summation-order contract)."""
+    import torch
+    enc = encode_cached(instance.categories, instance.agents)
+    ids, n = enc.agent_ids, enc.n
+    pos = getattr(enc, "_pos", None)
+    if pos is None:
+        pos = enc._pos = {aid: p for p, aid in enumerate(ids)}
+    pairs = list(zip(portfolio, probabilities))
+    x, rows = _membership([panel for panel, _ in pairs], n, pos.__getitem__)   # KeyError: agent not in the instance
+    weights = np.array([pob for _, pob in pairs], np.float64).reshape(-1)
+    m = n * (n - 1) // 2
+    tri = torch.empty(max(m, 1), dtype=torch.float64, device="cuda")
+    d_alloc = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")
+    _portfolio_launch(rows, weights, n, tri, d_alloc)
+    # the panel set while the device works: members in ascending position (np.nonzero walks row-major)
+    names = list(map(ids.__getitem__, np.nonzero(x)[1].tolist()))
+    ends = np.cumsum(np.count_nonzero(x, axis=1)).tolist()
+    panels = {tuple(names[a:b]) for a, b, (_, pob) in zip([0] + ends[:-1], ends, pairs)
+              if min_probability is None or pob > min_probability}
+    alloc = dict(zip(ids, d_alloc[:n].cpu().numpy().tolist()))          # the call's one host wait
+    return alloc, panels, PairHistogram._from_device_triangle(n, tri)
+
+
+def _solver(module, name):
+    """The reference's solver entry point if its module is importable; else ImportError naming the
+    ``find_distribution`` keyword."""
+    import importlib
+    try:
+        fn = getattr(importlib.import_module(module), name, None)
+    except ImportError:
+        fn = None
+    if fn is None:
+        raise ImportError("%s.%s is not importable (the solver stays in the reference and needs Gurobi): pass the "
+                          "solver as find_distribution=, called as find_distribution(categories, agents, "
+                          "columns_data, k, False, [])" % (module, name))
+    return fn
+
+
+def _solved_probabilities(instance, find_distribution, min_probability):
+    columns_data = {agent_id: {} for agent_id in instance.agents}
+    portfolio, output_probs, _ = find_distribution(instance.categories, instance.agents, columns_data, instance.k,
+                                                   False, [])
+    return portfolio_probabilities(instance, portfolio, output_probs, min_probability=min_probability)
+
+
+def leximin_probabilities(instance: Instance, find_distribution=None) -> Tuple[ProbAllocation, set, PairHistogram]:
+    """analysis.py:194-210: the exact probability allocation for LEXIMIN.  ``find_distribution`` is the
+    solver (default: the reference's ``leximin.find_distribution_leximin`` when importable, else
+    ImportError), called as the reference calls it; the rest is ``portfolio_probabilities`` with
+    the reference's ``1e-11`` threshold on the returned set of panels."""
+    if find_distribution is None:
+        find_distribution = _solver("leximin", "find_distribution_leximin")
+    return _solved_probabilities(instance, find_distribution, 0.00000000001)
+
+
+def xmin_probabilities(instance: Instance, find_distribution=None) -> Tuple[ProbAllocation, set, PairHistogram]:
+    """analysis.py:213-228: the same for XMIN (default solver: the reference's
+    ``xmin.find_distribution_xmin``); every panel of the portfolio is in the returned set."""
+    if find_distribution is None:
+        find_distribution = _solver("xmin", "find_distribution_xmin")
+    return _solved_probabilities(instance, find_distribution, None)

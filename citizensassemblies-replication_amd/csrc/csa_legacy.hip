@@ -15,6 +15,8 @@
 //                        (PairHistogram.add_portfolio_of_panels_to_histogram, analysis.py:90-95).
 //   unique_kernel        open-addressing table of panel indices keyed by a 128-bit panel
 //                        hash, exact full-bitmask compare (found_panels, analysis.py:171,186).
+// and, for the LEXIMIN / XMIN analysis side (analysis.py:194-228), portfolio_pairs_kernel
+// (portfolio.inc): float64 sums of panel probabilities per pair and person, in portfolio order.
 // The C ABI is declared in include/csa_legacy.h.
 #include <hip/hip_runtime.h>
 
@@ -1744,6 +1746,8 @@ __global__ __launch_bounds__(256) void pair_histogram_lds_kernel(const int64_t *
     if (threadIdx.x == 0 && over_s) atomicAdd(overflow, (unsigned long long)over_s);
 }
 
+#include "portfolio.inc"
+
 }  // namespace
 
 // library-internal: lets legacy_mt.cpp set the csa_last_error() message
@@ -2788,6 +2792,34 @@ int csa_pairs_upper_async(const int64_t *d_pairs, int32_t n, double divisor, voi
     else
         hipLaunchKernelGGL(pairs_upper_kernel<false>, dim3((unsigned)(n - 1)), dim3(256), 0, (hipStream_t)stream, d_pairs,
                            n, 0.0, d_out);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+// Portfolio probabilities (analysis.py:90-95 and 204-207): portfolio_pairs_kernel over the XT planes.
+// Every argument is checked on the host before any device call.
+int csa_portfolio_pairs_async(const uint64_t *d_xt, uint64_t n_panels, int32_t n, const double *d_weights,
+                              double *d_upper, double *d_alloc, uint32_t flags, void *stream) {
+    if (n < 0) return fail(CSA_E_INVALID, "portfolio pairs: invalid n = %d", n);
+    if (flags & ~CSA_PORTFOLIO_ACCUMULATE) return fail(CSA_E_INVALID, "portfolio pairs: invalid flags 0x%x", flags);
+    if (!d_upper && !d_alloc) return fail(CSA_E_INVALID, "portfolio pairs: invalid outputs (d_upper and d_alloc both NULL)");
+    if (n_panels > 0 && (!d_xt || !d_weights))
+        return fail(CSA_E_INVALID, "portfolio pairs: invalid NULL d_xt or d_weights with %llu panels",
+                    (unsigned long long)n_panels);
+    const bool accumulate = (flags & CSA_PORTFOLIO_ACCUMULATE) != 0;
+    if (n == 0) return CSA_OK;
+    const uint64_t npairs = (uint64_t)n * (uint64_t)(n - 1) / 2;
+    if (n_panels == 0) {  // nothing to add: the stored values stay, or a zero fill (+0.0 is all-zero bits)
+        if (accumulate) return CSA_OK;
+        if (d_upper && npairs) HIPCHK(hipMemsetAsync(d_upper, 0, npairs * 8, (hipStream_t)stream));
+        if (d_alloc) HIPCHK(hipMemsetAsync(d_alloc, 0, (size_t)n * 8, (hipStream_t)stream));
+        return CSA_OK;
+    }
+    const uint64_t nt = ((uint64_t)n + kPfTile - 1) / kPfTile, ntri = nt * (nt + 1) / 2;
+    if (ntri > 0x7FFFFFFFull) return fail(CSA_E_UNSUPPORTED, "portfolio pairs: n = %d needs %llu tiles", n, (unsigned long long)ntri);
+    hipLaunchKernelGGL(portfolio_pairs_kernel, dim3((unsigned)ntri), dim3(kPfThreads), 0, (hipStream_t)stream,
+                       reinterpret_cast<const uint32_t *>(d_xt), n_panels, n, csa_xt_pad(n), d_weights, d_upper, d_alloc,
+                       accumulate ? 1 : 0);
     HIPCHK(hipGetLastError());
     return CSA_OK;
 }

@@ -8,7 +8,9 @@
   33.5 M at n = 8192).  For a LEGACY histogram the pair counts are integers <= S, so the
   sorted list is a histogram of the counts: ``pair_histogram_kernel`` bins the upper
   triangle on the device and the host expands ``v / S`` (float64 true division, as the
-  reference) ``hist[v]`` times.  Float histograms (LEXIMIN / XMIN portfolios, uniform) are
+  reference) ``hist[v]`` times.  A LEXIMIN / XMIN portfolio histogram built by
+  ``analysis.portfolio_probabilities`` whose float64 triangle is still on the device is sorted
+  there (``torch.sort``) and copied once; other float histograms (uniform, host-built) are
   sorted on the host.
 """
 import ctypes
@@ -75,7 +77,14 @@ def sorted_pair_probabilities(pair_histogram, device="cuda"):
     """Ascending list of all pair values of a PairHistogram (analysis.py:339-342), as float64."""
     counts, S = getattr(pair_histogram, "_counts", None), getattr(pair_histogram, "_S", None)
     if counts is None or S is None:
-        return np.sort(pair_histogram.upper())      # float histogram: not a LEGACY count matrix
+        tri = getattr(pair_histogram, "_dtri", None)
+        if tri is not None and pair_histogram._uv is None and not pair_histogram._divs:
+            # a LEXIMIN / XMIN portfolio histogram whose triangle is still on the device
+            # (analysis.portfolio_probabilities): sorted there, one copy of the sorted values
+            import torch
+            m = len(pair_histogram)
+            return torch.sort(tri[:m]).values.cpu().numpy()
+        return np.sort(pair_histogram.upper())      # any other float histogram: sorted on the host
     import torch
     n = counts.shape[0]
     if isinstance(counts, np.ndarray):

@@ -398,6 +398,28 @@ int csa_pairs_upper_async(const int64_t *d_pairs, int32_t n, double divisor, voi
  * pair counts (every panel contributes x_i * x_i = x_i): d_counts[i] = d_pairs[i*n + i] (stored). */
 int csa_pairs_diag_async(const int64_t *d_pairs, int32_t n, int64_t *d_counts, void *stream);
 
+/* Portfolio probabilities: the work leximin_probabilities / xmin_probabilities do after the solver
+ * returns (portfolio, probabilities) -- PairHistogram.add_portfolio_of_panels_to_histogram
+ * (analysis.py:90-95) and the selection_probs loop (analysis.py:204-207, 222-225).  d_xt: the XT
+ * planes of the portfolio's n_panels packed panels exactly as csa_transpose_count_async writes them;
+ * d_weights: n_panels float64 probabilities in portfolio order.  Outputs (either may be NULL, not
+ * both): d_upper, the strict upper triangle packed in the reference's key order (pair (i, j), i < j,
+ * at i(n-1) - i(i-1)/2 + j-i-1; n(n-1)/2 float64), and d_alloc, the n per-person values (the
+ * diagonal).
+ * Summation-order contract: every output value starts from +0.0 -- with CSA_PORTFOLIO_ACCUMULATE
+ * from the value stored in the output -- and receives d_weights[p] for each panel p that holds both
+ * agents (the agent, for d_alloc), in ASCENDING p, one IEEE float64 addition each, as the reference's
+ * `+=` per panel does: no reassociation, no tree reduction, no atomics, so the results are the
+ * reference's floats bit for bit (float64 addition does not associate; a matrix product or a
+ * reversed sum differs in the last bits).
+ * Stream-ordered, no host wait.  n_panels == 0 leaves the outputs as they are with
+ * CSA_PORTFOLIO_ACCUMULATE and zero-fills them without.  CSA_E_INVALID, before any device call, for
+ * n < 0, a NULL d_xt or d_weights with n_panels > 0, both outputs NULL, or unknown flag bits. */
+#define CSA_PORTFOLIO_ACCUMULATE 1u
+int csa_portfolio_pairs_async(const uint64_t *d_xt, uint64_t n_panels, int32_t n, const double *d_weights,
+                              double *d_upper /* n(n-1)/2 or NULL */, double *d_alloc /* n or NULL */,
+                              uint32_t flags, void *stream);
+
 /* Decode a device status block (host copy of the 4 words) into a CSA_* code
  * and set csa_last_error() accordingly. */
 int csa_status_decode(const uint32_t *h_status);

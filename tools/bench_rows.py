@@ -5,8 +5,12 @@
   f2  cache.run_legacy_or_retrieve npz write / read at sf_e, 10^6 panels
   f3  pair_histogram_kernel (sorted pair-probability curve, analysis.py:339-342): kernel time and
       HBM GB/s over the upper triangle at sf_e (n=1727) and n=8192, vs numpy sort of the triangle
+  f3b analysis.portfolio_probabilities (the LEXIMIN / XMIN analysis side, analysis.py:194-228) at
+      sf_e with an XMIN-sized portfolio (5n panels): end to end, upload and triangle read included,
+      vs the host PairHistogram.add_portfolio_of_panels_to_histogram (median of 5, one process);
+      and portfolio_pairs_kernel alone, there and at n = 8192, P = 5n
 
-    python tools/bench_rows.py [--panels 1000000]
+    python tools/bench_rows.py [--panels 1000000] [--rows f1,f2,f3,f3b]
 """
 import argparse
 import ctypes
@@ -29,10 +33,94 @@ def paths(name):
     return os.path.join(INST, name, "categories.csv"), os.path.join(INST, name, "respondents.csv")
 
 
+def portfolio_weights(P):
+    """The goldens' weights (tools/make_portfolio_goldens.py): 12 binades, a 0.0, a 1e-13, sum 1."""
+    rs = np.random.RandomState(7)
+    w = rs.uniform(size=P) * 2.0 ** -rs.randint(0, 13, size=P).astype(np.float64)
+    rest = np.ones(P, bool)
+    rest[[P // 3, (2 * P) // 3]] = False
+    w[rest] *= (1.0 - 1e-13) / w[rest].sum()
+    w[P // 3], w[(2 * P) // 3] = 0.0, 1e-13
+    return [float(x) for x in w]
+
+
+def portfolio_kernel_ms(A, N, torch, rows, weights, n, reps=3):
+    """portfolio_pairs_kernel alone (XT and weights already on the device), ms per launch."""
+    L = N.lib()
+    P = len(weights)
+    st = torch.cuda.current_stream()
+    sp = ctypes.c_void_p(st.cuda_stream)
+    d_rows = torch.from_numpy(rows.view(np.int64).reshape(-1)).cuda()
+    w = torch.from_numpy(np.asarray(weights, np.float64)).cuda()
+    xt = torch.empty(((P + 63) // 64) * L.csa_xt_pad(n), dtype=torch.int64, device="cuda")
+    cnt = torch.zeros(n, dtype=torch.int64, device="cuda")
+    N.check(L.csa_transpose_count_async(N.ptr(d_rows), P, n, N.ptr(xt), N.ptr(cnt), sp))
+    tri = torch.empty(n * (n - 1) // 2, dtype=torch.float64, device="cuda")
+    al = torch.empty(n, dtype=torch.float64, device="cuda")
+    call = lambda: N.check(L.csa_portfolio_pairs_async(N.ptr(xt), P, n, N.ptr(w), N.ptr(tri), N.ptr(al), 0, sp))
+    call()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(st)
+    for _ in range(reps):
+        call()
+    e1.record(st)
+    torch.cuda.synchronize()
+    return {"kernel_ms": e0.elapsed_time(e1) / reps}
+
+
+def portfolio_row(P_, torch):
+    A = importlib.import_module(PKG + ".analysis")
+    N = importlib.import_module(PKG + "._native")
+    inst = P_.read_instance(*paths("sf_e_110"), 110)
+    n = len(inst.agents)
+    P = 5 * n
+    P_.seed(5)
+    portfolio = [frozenset(p) for p in A.legacy_find_batch(inst.categories, inst.agents, 110, P)]
+    weights = portfolio_weights(P)
+    pos = {a: q for q, a in enumerate(inst.agents)}
+    as_positions = [sorted(pos[a] for a in p) for p in portfolio]
+
+    def device_call():
+        alloc, panels, hist = A.portfolio_probabilities(inst, portfolio, weights)
+        return hist.upper()
+
+    def host_call():
+        h = A.PairHistogram(n)
+        h.add_portfolio_of_panels_to_histogram(as_positions, weights)
+        return h.upper()
+
+    def median5(fn):
+        ts = []
+        for _ in range(5):
+            t = time.perf_counter()
+            r = fn()
+            ts.append(time.perf_counter() - t)
+        return sorted(ts)[2], r
+    device_call()                                   # warm-up: library load, encode, allocator
+    dev_s, dev_u = median5(device_call)
+    host_s, host_u = median5(host_call)
+    row = {"instance": "sf_e_110", "n": n, "panels": P,
+           "device_end_to_end_ms": dev_s * 1e3, "host_method_ms": host_s * 1e3,
+           "bit_equal": bool(np.array_equal(dev_u.view(np.uint64), host_u.view(np.uint64))),
+           "note": "device: pack + upload + transpose + kernel + alloc read + panel set + triangle read; "
+                   "host: add_portfolio_of_panels_to_histogram alone (no alloc, no set)"}
+    row["kernel_sf_e"] = portfolio_kernel_ms(A, N, torch, A._pack_positions(as_positions, n), weights, n)
+    n2, k2 = 8192, 200
+    P2 = 5 * n2
+    rs = np.random.RandomState(11)     # Bernoulli(k / n) members: LEGACY's density without an instance's quotas
+    rows2 = np.concatenate([np.packbits(rs.rand(min(2048, P2 - o), n2) < k2 / n2, axis=1, bitorder="little")
+                            for o in range(0, P2, 2048)]).view("<u8").reshape(P2, n2 // 64)
+    row["kernel_n8192"] = dict(n=n2, panels=P2, density=k2 / n2, **portfolio_kernel_ms(
+        A, N, torch, rows2, portfolio_weights(P2), n2))
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--panels", type=int, default=10 ** 6)
+    ap.add_argument("--rows", default="f1,f2,f3,f3b", help="comma-separated rows to measure")
     args = ap.parse_args()
+    rows = set(args.rows.split(","))
     import torch
     P = importlib.import_module(PKG)
     X = importlib.import_module(PKG + ".xmin")
@@ -43,6 +131,11 @@ def main():
     from oracle import coracle
     from oracle.legacy_oracle import read_instance as oread
     out = {}
+    if "f3b" in rows:
+        out["f3b_portfolio"] = portfolio_row(P, torch)
+    if not rows & {"f1", "f2", "f3"}:
+        print(json.dumps(out))
+        return
 
     # ---- f1 -------------------------------------------------------------------------------
     inst = P.read_instance(*paths("sf_e_110"), 110)
