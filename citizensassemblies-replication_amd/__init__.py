@@ -15,6 +15,12 @@ plus the analysis side of LEXIMIN / XMIN after the solver (analysis.py:194-228):
 leximin_probabilities, xmin_probabilities (solver passed in or imported from the reference)
 and portfolio_probabilities, bit-equal float64 sums in portfolio order on the device
 
+plus what a run's panels look like as a whole: legacy_composition(instance, iterations, seed, groups)
+returns legacy_probabilities' results and a CompositionHistogram (per agent group -- feature_groups,
+intersection_groups, agent_groups -- how many panels hold 0, 1, ..., k of its members), counted on the
+device by group_hist_kernel; intersectional_representation gives the numbers of
+plot_intersectional_representation (analysis.py:459-530)
+
 plus xmin._get_panel_not_in_portfolio_if_possible (XMIN's LEGACY caller,
 xmin.py:464-474) on the device.
 """
@@ -22,9 +28,13 @@ from .instance import Instance, read_instance, encode  # noqa: F401
 from .legacy import SelectionError, check_min_cats, find_random_sample_legacy, seed, set_rng_mode  # noqa: F401
 from .analysis import PairHistogram, PanelSet, legacy_find, legacy_find_batch, legacy_probabilities  # noqa: F401
 from .analysis import leximin_probabilities, portfolio_probabilities, xmin_probabilities  # noqa: F401
+from .analysis import legacy_composition  # noqa: F401
+from .stats import (CompositionHistogram, GroupSet, agent_groups, feature_groups, group_composition,  # noqa: F401
+                    intersection_groups, intersectional_representation)
 from . import _native, xmin  # noqa: F401
 
 __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_cats",
            "find_random_sample_legacy", "seed", "set_rng_mode", "PairHistogram", "PanelSet", "legacy_find",
            "legacy_find_batch", "legacy_probabilities", "leximin_probabilities", "xmin_probabilities",
-           "portfolio_probabilities"]
+           "portfolio_probabilities", "legacy_composition", "CompositionHistogram", "GroupSet", "agent_groups",
+           "feature_groups", "group_composition", "intersection_groups", "intersectional_representation"]

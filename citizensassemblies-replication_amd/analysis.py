@@ -401,9 +401,10 @@ class LegacyRaw:
     """Integer results of one legacy_probabilities run (exact, before division).  ``stats``: the
     run's draw statistics (attempts, SelectionErrors, min-quota rejections; see draw_stats)."""
 
-    def __init__(self, counts, pairs, unique, panels, attempts, stats=None):
+    def __init__(self, counts, pairs, unique, panels, attempts, stats=None, composition=None):
         self.counts, self.pairs, self.unique, self.panels, self.attempts = counts, pairs, unique, panels, attempts
         self.stats = stats
+        self.composition = composition     # host int64[G, k + 1] when the run was given groups
 
 
 STAT_KEYS = ("attempts", "selection_errors", "rejections")
@@ -487,7 +488,7 @@ def cached_pipeline(enc, k, chunk):
 
 
 def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20, host_panels=None,
-                         host_stats=None):
+                         host_stats=None, groups=None):
     """One legacy_probabilities batch on the device through a DevicePipeline cached with the
     encoding (picks / XT / scratch buffers reused across calls).  Panels and hashes of the whole
     batch go to fresh device tensors (the exact distinct count needs all of them; with
@@ -495,7 +496,10 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
     iterated).  Returns LegacyRaw with host counts and device pair counts (PairHistogram
     materialises them lazily).  ``host_panels`` (uint64[S, W], MT mode: drawn on the host)
     replaces the device draw; the counting, pairs and distinct count still run on the device
-    (``host_stats``: that draw's statistics)."""
+    (``host_stats``: that draw's statistics).  ``groups`` (a stats.GroupSet): group_hist_kernel also
+    runs over the batch's panels, after the draws, on the stream of the distinct count -- beside the
+    counting and pairs with device draws -- and its int64[G, k + 1] table comes back in the same host
+    copy (``LegacyRaw.composition``); its status lands in the same status block."""
     import torch
     from .distributed import HashTable
     S = int(S)
@@ -522,6 +526,12 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
         if table is None or table.device != dev:
             table = enc._table = HashTable(S, dev)
         table.ensure(S)
+        n_hist = 0
+        if groups is not None:
+            if groups.W != W:
+                raise ValueError("groups of another encoding: W = %d, the instance has %d" % (groups.W, W))
+            n_hist = len(groups) * (int(k) + 1)
+            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
         try:
             drawn = None  # what the distinct count's side stream waits for: the draws
             if one:
@@ -572,6 +582,10 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
                 N.check(N.lib().csa_unique_async(N.ptr(hashes), N.ptr(panels), S, W, N.ptr(table.table), table.slots,
                                                  N.ptr(table.count), N.ptr(pipe.status),
                                                  ctypes.c_void_p(ust.cuda_stream)))
+                if groups is not None:
+                    from .stats import group_hist_device
+                    d_hist = torch.zeros(max(n_hist, 1), dtype=torch.int64, device=dev)
+                    group_hist_device(panels, S, W, d_masks, len(groups), int(k) + 1, d_hist, pipe.status, ust)
             if ust is not pipe.stream:
                 pipe.stream.wait_stream(ust)
             # counts, distinct count, draw statistics and status in ONE copy: the call's one host wait
@@ -581,6 +595,8 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
                 N.check(N.lib().csa_instance_draw_stats_async(enc.handle, N.ptr(st_d),
                                                               ctypes.c_void_p(pipe.stream.cuda_stream)))
                 parts.append(st_d)
+            if groups is not None:
+                parts.append(d_hist[:n_hist])
             h = torch.cat(parts + [pipe.status.to(torch.int64)]).cpu().numpy()
             n_ = enc.n
             status = (h[-4:] & 0xFFFFFFFF).astype(np.uint32)
@@ -592,10 +608,12 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
             counts = h[:n_].copy()
             unique = int(h[n_])
             stats = dict(zip(STAT_KEYS, (int(x) for x in h[n_ + 1:n_ + 4]))) if host_panels is None else host_stats
+            comp = h[len(h) - 4 - n_hist:len(h) - 4].reshape(len(groups), int(k) + 1).copy() if groups is not None \
+                else None
         finally:
             pipe.panels, pipe.hashes, pipe.pairs = own_p, own_h, own_pairs
     return LegacyRaw(counts, pairs.view(enc.n, enc.n), unique, panels[: S * W] if keep_panels else None, None,
-                     stats)
+                     stats, comp)
 
 
 def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
@@ -620,6 +638,12 @@ def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
     A sharded run's found_panels hold no panels: reading them on any rank re-draws the job's panels
     on that rank's GPU (``distributed.PanelRedraw``), without a collective.
     """
+    return _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, None)[:3]
+
+
+def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, groups):
+    """legacy_probabilities' body; with ``groups`` (a stats.GroupSet) the run also counts the panels'
+    composition.  Returns (alloc, found_panels, pair_histogram, CompositionHistogram or None)."""
     from . import distributed as D
     mode = rng or _legacy.RNG_MODE
     if mode not in ("philox", "mt"):
@@ -634,19 +658,49 @@ def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
         st = np.zeros(3, np.uint64)
         picks, panels, _ = mt_draw(enc, instance.k, S, stats=st)
         raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, host_panels=panels,
-                                   host_stats=dict(zip(STAT_KEYS, (int(x) for x in st))))
-        return finish(instance, enc, raw, S)
+                                   host_stats=dict(zip(STAT_KEYS, (int(x) for x in st))), groups=groups)
+        return finish(instance, enc, raw, S) + (composition(groups, raw, S, instance.k),)
     if D.world_size() > 1:
-        return D.legacy_probabilities_distributed(instance, iterations, random_seed, keep_panels=keep_panels)
+        out = D.legacy_probabilities_distributed(instance, iterations, random_seed, keep_panels=keep_panels,
+                                                 groups=groups)
+        return out if groups is not None else out + (None,)
     seed(random_seed)
     enc.check_quotas(instance.k)
     STREAM.take_panels(S)
     if devices is not None:
         raw = legacy_sample_raw(enc, instance.k, S, random_seed, want_pairs=True, want_panels=keep_panels,
                                 devices=devices)
-        return finish(instance, enc, raw, S)
-    raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels)
-    return finish(instance, enc, raw, S)
+        return finish(instance, enc, raw, S) + (None,)
+    raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, groups=groups)
+    return finish(instance, enc, raw, S) + (composition(groups, raw, S, instance.k),)
+
+
+def composition(groups, raw, S, k):
+    """The CompositionHistogram of a run that was given groups (None without)."""
+    if groups is None:
+        return None
+    from .stats import CompositionHistogram
+    return CompositionHistogram(groups.labels, raw.composition, S, k)
+
+
+def legacy_composition(instance: Instance, iterations: int, random_seed: int, groups, *, rng: str = None,
+                       keep_panels: bool = True):
+    """``legacy_probabilities`` plus what its panels look like as a whole: returns
+    ``(alloc, found_panels, pair_histogram, composition)``.
+
+    The first three are what ``legacy_probabilities(instance, iterations, random_seed, rng=rng,
+    keep_panels=keep_panels)`` returns, bit for bit (the same draws: a panel is a pure function of
+    seed and panel index).  ``composition`` is a ``stats.CompositionHistogram`` over ``groups`` (a
+    ``stats.GroupSet``: ``feature_groups``, ``intersection_groups``, ``agent_groups``, or their sum):
+    per group, how many of the run's panels hold 0, 1, ..., k of its members -- group_hist_kernel over
+    the drawn panels while they are in device memory, its table returned in the call's one host copy.
+    ``rng="mt"`` runs the same pass over the host-drawn panels.  With torch.distributed initialised
+    and world size > 1 the call is sharded like ``legacy_probabilities`` and every rank returns the
+    whole job's table (summed over the ranks)."""
+    from .stats import GroupSet
+    if not isinstance(groups, GroupSet):
+        raise TypeError("groups must be a stats.GroupSet")
+    return _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, groups)
 
 
 def finish(instance, enc, raw, S):

@@ -1747,6 +1747,7 @@ __global__ __launch_bounds__(256) void pair_histogram_lds_kernel(const int64_t *
 }
 
 #include "portfolio.inc"
+#include "composition.inc"
 
 }  // namespace
 
@@ -2820,6 +2821,39 @@ int csa_portfolio_pairs_async(const uint64_t *d_xt, uint64_t n_panels, int32_t n
     hipLaunchKernelGGL(portfolio_pairs_kernel, dim3((unsigned)ntri), dim3(kPfThreads), 0, (hipStream_t)stream,
                        reinterpret_cast<const uint32_t *>(d_xt), n_panels, n, csa_xt_pad(n), d_weights, d_upper, d_alloc,
                        accumulate ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+// Group composition (quota / intersection histograms): group_hist_kernel over the packed panels.
+// Every argument is checked on the host before any device call.
+int csa_group_hist_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W, const uint64_t *d_masks,
+                         int32_t n_groups, int32_t bins, int64_t *d_hist, uint32_t *d_status, void *stream) {
+    if (W <= 0) return fail(CSA_E_INVALID, "group hist: invalid W = %d", W);
+    if (n_groups < 0) return fail(CSA_E_INVALID, "group hist: invalid n_groups = %d", n_groups);
+    if (bins < 1) return fail(CSA_E_INVALID, "group hist: invalid bins = %d", bins);
+    if (n_panels == 0 || n_groups == 0) return CSA_OK;
+    if (!d_panels || !d_masks || !d_hist || !d_status)
+        return fail(CSA_E_INVALID, "group hist: invalid NULL d_panels, d_masks, d_hist or d_status");
+    if (W > kGhMaxW)
+        return fail(CSA_E_UNSUPPORTED, "group hist: W = %d words; one group's mask must fit %d bytes of LDS (W <= %d)", W,
+                    kGhMaskBytes, kGhMaxW);
+    int slab = 64;
+    while (slab * W * 8 > kGhMaskBytes) slab >>= 1;
+    const size_t mask_bytes = (size_t)slab * W * 8, tab_bytes = (size_t)slab * (size_t)(bins | 1) * 4;
+    const bool use_table = mask_bytes + tab_bytes <= (size_t)kGhLdsBytes;
+    const size_t lds = mask_bytes + (use_table ? tab_bytes : 0);
+    const unsigned nslab = ((unsigned)n_groups + slab - 1) / slab;
+    // panel ranges: about kGhTargetBlocks workgroups in all, none with fewer than two passes of its waves,
+    // and none with 2^31 panels or more (the table's entries are u32)
+    uint64_t ranges = std::max<uint64_t>(1, kGhTargetBlocks / nslab);
+    ranges = std::min(ranges, (n_panels + 4 * kGhWaves - 1) / (4 * kGhWaves));
+    ranges = std::max(ranges, (n_panels >> 31) + 1);
+    if (ranges > 65535)
+        return fail(CSA_E_UNSUPPORTED, "group hist: %llu panels in one call (at most 2^46)", (unsigned long long)n_panels);
+    hipLaunchKernelGGL(group_hist_kernel, dim3(nslab, (unsigned)ranges), dim3(kGhThreads), lds, (hipStream_t)stream,
+                       d_panels, n_panels, (int)W, d_masks, (int)n_groups, (int)bins, slab, use_table ? 1 : 0,
+                       reinterpret_cast<unsigned long long *>(d_hist), d_status);
     HIPCHK(hipGetLastError());
     return CSA_OK;
 }

@@ -465,7 +465,7 @@ def shard_device():
 
 
 def legacy_probabilities_distributed(instance, iterations, random_seed, keep_panels=True, chunk=None,
-                                     timings=None):
+                                     timings=None, groups=None):
     """analysis.py:162-191 with the panels sharded over the ranks of the default group.  Every rank
     returns the whole job's alloc, pair histogram and exact distinct-panel count.
 
@@ -485,7 +485,10 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
     exchange): the panels of the call are the whole run's and stay on the device, decoded when read, as
     the one-GPU call does.  ``keep_panels=False``: len() only.  The draw statistics
     (analysis.LAST_RUN_STATS) are summed over ranks.  ``timings`` (a dict) gets the host-side stage
-    times in ms."""
+    times in ms.  ``groups`` (a stats.GroupSet; analysis.legacy_composition's sharded form): every rank
+    runs group_hist_kernel over its share and the tables are summed in one more all_reduce; the call
+    then returns a fourth value, the CompositionHistogram of the whole job on every rank -- never a
+    share's."""
     import time
     import torch
     import torch.distributed as dist
@@ -505,12 +508,12 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
     dev = shard_device()
     with torch.cuda.device(dev):
         out = _sharded_call(A, N, dist, enc, k, S, random_seed, world, begin, local, n_max, dev, keep_panels, chunk,
-                            t0, timings, instance)
+                            t0, timings, instance, groups)
     return out
 
 
 def _sharded_call(A, N, dist, enc, k, S, random_seed, world, begin, local, n_max, dev, keep_panels, chunk, t0, timings,
-                  instance):
+                  instance, groups=None):
     import time
     import torch
     C = max(1, min(max(local, 1), int(chunk or os.environ.get("CSA_SHARD_CHUNK", 1 << 20))))
@@ -547,6 +550,17 @@ def _sharded_call(A, N, dist, enc, k, S, random_seed, world, begin, local, n_max
             pipe.counts, pipe.pairs = own_counts, own_pairs
         # this shard's draw statistics, before the exchange's re-draws (device, no host wait)
         N.check(L.csa_instance_draw_stats_async(enc.handle, N.ptr(acc[n:n + 3]), sp))
+        n_hist = 0
+        if groups is not None:
+            # the share's composition table on the pipeline stream (ordered after every draw); with
+            # more than one rank (or a forced exchange) the tables are summed below
+            from .stats import group_hist_device
+            if groups.W != W:
+                raise ValueError("groups of another encoding: W = %d, the instance has %d" % (groups.W, W))
+            n_hist = len(groups) * (k + 1)
+            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
+            d_hist = torch.zeros(max(n_hist, 1), dtype=torch.int64, device=dev)
+            group_hist_device(panels, local, W, d_masks, len(groups), k + 1, d_hist, pipe.status, st)
         if ex is not None:
             # a shard whose draw failed still enters the collectives (every rank must, or the others
             # hang); its status block joins the MAX all_reduce below, so every rank raises the draw's
@@ -574,13 +588,15 @@ def _sharded_call(A, N, dist, enc, k, S, random_seed, world, begin, local, n_max
         code = pipe.status[:1].to(torch.int64)
         if ex is not None:
             _all_reduce(acc)
+            if groups is not None:
+                _all_reduce(d_hist)
             # MAX over ranks of a priority key: a draw error (KeyError / attempt limit) on any rank
             # outranks an exchange error on another (an overflowing segment), whatever their codes
             code += ERR_DRAW_PRIORITY * ((code == N.CSA_E_NO_CANDIDATE) | (code == N.CSA_E_ATTEMPT_LIMIT))
             _all_reduce(code, op=dist.ReduceOp.MAX)
             code %= ERR_DRAW_PRIORITY
         tail = torch.cat([code, pipe.status.to(torch.int64)])
-        host = torch.cat([acc, tail]).cpu()          # the call's one host wait
+        host = torch.cat([acc, tail] + ([d_hist[:n_hist]] if groups is not None else [])).cpu()  # the one host wait
     t2 = time.perf_counter()
     h = host.numpy()
     if int(h[n + 4]):
@@ -590,8 +606,10 @@ def _sharded_call(A, N, dist, enc, k, S, random_seed, world, begin, local, n_max
     # one rank (no exchange): its panels are the whole run's, so found_panels keeps them on the device and
     # decodes them when iterated, as the one-GPU call does
     solo = ex is None and keep_panels
-    raw = A.LegacyRaw(counts, pairs.view(n, n), int(h[n + 3]), panels[: local * W] if solo else None, None, stats)
-    out = A.finish(instance, enc, raw, S)
+    comp = h[n + 9:n + 9 + n_hist].reshape(len(groups), k + 1).copy() if groups is not None else None
+    raw = A.LegacyRaw(counts, pairs.view(n, n), int(h[n + 3]), panels[: local * W] if solo else None, None, stats,
+                      comp)
+    out = A.finish(instance, enc, raw, S) + ((A.composition(groups, raw, S, k),) if groups is not None else ())
     if keep_panels and not solo:
         # nothing kept, nothing sent: the whole job's panels are re-drawn where they are read
         out[1]._redraw = PanelRedraw(device_redraw(enc, k, random_seed, dev), S, W, chunk=max(C, 1 << 16))

@@ -95,3 +95,318 @@ def sorted_pair_probabilities(pair_histogram, device="cuda"):
     # matrices whose diagonal was not kept as well
     n_bins = int(torch.triu(d).max().item()) + 1 if n else 1
     return sorted_counts_to_probabilities(pair_count_histogram(d.contiguous().view(-1), n, n_bins), S)
+
+
+# ---- group composition: what a panel looks like as a whole ----------------------------------------
+#
+# A group is a set of agents held as a uint64[W] bitmask in encoding order (agent p = bit p & 63 of
+# word p >> 6, padding bits zero): a quota feature, a two-feature intersection
+# (plot_intersectional_representation, analysis.py:459-530), a household.  ``group_composition``
+# counts, per group, the panels that hold 0, 1, ..., k of its members -- group_hist_kernel
+# (csrc/composition.inc) on the device, the numpy implementation below without one.
+
+class GroupSet:
+    """``labels`` (list), ``masks`` uint64[G, W], ``sizes`` int64[G] (members per group).  ``a + b``
+    concatenates two sets over the same encoding."""
+
+    def __init__(self, labels, masks, sizes=None):
+        self.labels = list(labels)
+        m = np.ascontiguousarray(masks, np.uint64)
+        assert m.ndim == 2 and m.shape[0] == len(self.labels)
+        self.masks = m
+        self.sizes = _popcount_rows(m) if sizes is None else np.asarray(sizes, np.int64)
+
+    @property
+    def W(self):
+        return self.masks.shape[1]
+
+    def __len__(self):
+        return len(self.labels)
+
+    def __add__(self, other):
+        if not isinstance(other, GroupSet):
+            return NotImplemented
+        if other.W != self.W:
+            raise ValueError("group sets of different encodings: W = %d and %d" % (self.W, other.W))
+        return GroupSet(self.labels + other.labels, np.concatenate([self.masks, other.masks]),
+                        np.concatenate([self.sizes, other.sizes]))
+
+
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.int64)
+
+
+def _popcount_rows(words):
+    """Set bits per row of a uint64[R, W] array."""
+    w = np.ascontiguousarray(words, np.uint64)
+    return _POP8[w.view(np.uint8).reshape(w.shape[0], -1)].sum(axis=1)
+
+
+def _pack_members(member, W):
+    """bool[G, n] membership -> uint64[G, W] masks (padding bits zero)."""
+    G, n = member.shape
+    x = np.zeros((G, max(W, 1) * 64), np.bool_)
+    x[:, :n] = member
+    return np.ascontiguousarray(np.packbits(x, axis=1, bitorder="little")).view("<u8").reshape(G, max(W, 1))
+
+
+def _encoding(instance):
+    from .instance import encode_cached
+    return encode_cached(instance.categories, instance.agents)
+
+
+def _feature_membership(enc):
+    """bool[F, n]: agent p holds feature f (each agent one feature per category)."""
+    member = np.zeros((enc.F, enc.n), np.bool_)
+    if enc.n:
+        for c in range(enc.C):
+            member[enc.person_feat[:, c], np.arange(enc.n)] = True
+    return member
+
+
+def feature_groups(instance):
+    """One group per (category, feature), in ``EncodedInstance.feat_keys`` order."""
+    enc = _encoding(instance)
+    member = _feature_membership(enc)
+    return GroupSet(list(enc.feat_keys), _pack_members(member, enc.W), member.sum(axis=1))
+
+
+def read_intersections(path):
+    """Rows of an ``intersections.csv``-shaped table as ((c1, f1), (c2, f2), population share)."""
+    import csv
+    rows = []
+    with open(path, "r", encoding="utf-8") as fh:
+        for entry in csv.DictReader(fh):
+            rows.append(((entry["category 1"], entry["feature 1"]), (entry["category 2"], entry["feature 2"]),
+                         float(entry["population share"])))
+    return rows
+
+
+def _intersection_rows(rows):
+    import os
+    if isinstance(rows, (str, os.PathLike)):
+        return [(a, b) for a, b, _ in read_intersections(rows)]
+    return [(tuple(r[0]), tuple(r[1])) for r in rows]
+
+
+def _feature_index(enc):
+    """(category, feature) -> feature id; KeyError on an unknown category or feature."""
+    fid = {key: f for f, key in enumerate(enc.feat_keys)}
+    cats = set(enc.cat_names)
+
+    def index(key):
+        key = tuple(key)
+        if key[0] not in cats or key not in fid:
+            raise KeyError(key[0] if key[0] not in cats else key[1])
+        return fid[key]
+    return index
+
+
+def intersection_groups(instance, rows):
+    """One group per two-feature intersection: ``rows`` is a path to an ``intersections.csv``-shaped
+    table or an iterable of ``((c1, f1), (c2, f2))``; the mask is the AND of the two feature masks
+    (has_features, analysis.py:459-463).  Empty groups are kept; an unknown category or feature
+    raises KeyError."""
+    enc = _encoding(instance)
+    index = _feature_index(enc)
+    pairs = _intersection_rows(rows)
+    member = _feature_membership(enc)
+    both = np.zeros((len(pairs), enc.n), np.bool_)
+    for g, (a, b) in enumerate(pairs):
+        both[g] = member[index(a)] & member[index(b)]
+    return GroupSet(pairs, _pack_members(both, enc.W), both.sum(axis=1))
+
+
+def agent_groups(instance, groups):
+    """Arbitrary agent sets ``{label: agent ids}`` (the rings of ``legacy.address_rings``, households);
+    an id that is not in the instance raises KeyError."""
+    enc = _encoding(instance)
+    pos = {aid: p for p, aid in enumerate(enc.agent_ids)}
+    labels = list(groups)
+    member = np.zeros((len(labels), enc.n), np.bool_)
+    for g, label in enumerate(labels):
+        for aid in groups[label]:
+            member[g, pos[aid]] = True
+    return GroupSet(labels, _pack_members(member, enc.W), member.sum(axis=1))
+
+
+def group_hist_host(masks, panels, bins):
+    """csa_group_hist_async's contract in numpy: int64[G, bins], hist[g][c] = number of panels with
+    popcount(panel & mask_g) == c.  A count >= bins raises CsaError(CSA_E_INVALID), as the device's
+    status block does.  The counts are a 0/1 matrix product (float32 sums of at most 64 W ones: exact)."""
+    masks = np.ascontiguousarray(masks, np.uint64)
+    panels = np.ascontiguousarray(panels, np.uint64)
+    G, W = masks.shape
+    S = panels.shape[0]
+    assert panels.ndim == 2 and (S == 0 or panels.shape[1] == W)
+    bins = int(bins)
+    hist = np.zeros((G, bins), np.int64)
+    if G == 0 or S == 0:
+        return hist
+    assert 64 * W < 1 << 24
+    m = np.unpackbits(masks.view(np.uint8).reshape(G, -1), axis=1, bitorder="little").astype(np.float32)
+    base = np.arange(G, dtype=np.int64) * bins
+    step = max(1, (1 << 24) // (64 * W))
+    for off in range(0, S, step):
+        x = np.unpackbits(panels[off:off + step].view(np.uint8).reshape(-1, 8 * W), axis=1, bitorder="little")
+        c = (x.astype(np.float32) @ m.T).astype(np.int64)                   # [panels, G]
+        bad = np.argwhere(c >= bins)
+        if len(bad):
+            raise N.CsaError(N.CSA_E_INVALID, "group hist: panel %d holds %d members of group %d, bins = %d"
+                             % (off + bad[0][0], c[bad[0][0], bad[0][1]], bad[0][1], bins))
+        hist += np.bincount((c + base).ravel(), minlength=G * bins).reshape(G, bins)
+    return hist
+
+
+class CompositionHistogram:
+    """``counts[g][c]`` = panels of the run holding exactly c members of group g (host int64[G, k+1]),
+    over ``S`` panels of size ``k``; ``labels`` name the groups.  Everything derived is float64 from
+    the integer counts.  ``a + b`` merges two runs with equal labels and k (exact: integers).  Holds
+    host arrays only, so it pickles and loads where no GPU is visible."""
+
+    def __init__(self, labels, counts, S, k):
+        self.labels = list(labels)
+        self.counts = np.ascontiguousarray(counts, np.int64)
+        self.S, self.k = int(S), int(k)
+        assert self.counts.shape == (len(self.labels), self.k + 1)
+
+    def __len__(self):
+        return len(self.labels)
+
+    def __add__(self, other):
+        if not isinstance(other, CompositionHistogram):
+            return NotImplemented
+        if other.labels != self.labels or other.k != self.k:
+            raise ValueError("composition histograms over different groups or panel sizes")
+        return CompositionHistogram(self.labels, self.counts + other.counts, self.S + other.S, self.k)
+
+    def probabilities(self):
+        """P(a panel holds c members), float64[G, k+1] = counts / S."""
+        return self.counts / self.S
+
+    def mean(self):
+        """Expected members per panel (by linearity also the sum of the members' marginals)."""
+        return (self.counts * np.arange(self.k + 1, dtype=np.int64)).sum(axis=1) / self.S
+
+    def panel_share(self):
+        """mean / k: the panel share plot_intersectional_representation reports."""
+        return self.mean() / self.k
+
+    def variance(self):
+        """Variance of the members per panel (population form: the S panels are the distribution)."""
+        d = np.arange(self.k + 1, dtype=np.float64)[None, :] - self.mean()[:, None]
+        return (self.counts * d * d).sum(axis=1) / self.S
+
+    def prob_absent(self):
+        """P(a panel holds no member of the group)."""
+        return self.counts[:, 0] / self.S
+
+    def support(self):
+        """(lowest, highest) non-empty bin per group, int64[G] each; (-1, -1) for a run of no panels."""
+        nz = self.counts != 0
+        some = nz.any(axis=1)
+        lo = np.where(some, nz.argmax(axis=1), -1)
+        hi = np.where(some, self.k - nz[:, ::-1].argmax(axis=1), -1)
+        return lo.astype(np.int64), hi.astype(np.int64)
+
+
+def _is_device_tensor(a):
+    return hasattr(a, "is_cuda") and a.is_cuda
+
+
+def group_hist_device(d_panels, S, W, d_masks, G, bins, d_hist, d_status, stream):
+    """Enqueue csa_group_hist_async on ``stream`` (a torch stream); nothing waits."""
+    N.check(N.lib().csa_group_hist_async(N.ptr(d_panels), int(S), int(W), N.ptr(d_masks), int(G), int(bins),
+                                         N.ptr(d_hist), N.ptr(d_status), ctypes.c_void_p(stream.cuda_stream)))
+
+
+def group_composition(groups, panels, k, stream=None):
+    """Composition of ``panels`` (packed host uint64[S, W], or the device tensor a run kept: int64 /
+    uint64 words, S*W of them) over ``groups``: a CompositionHistogram with k + 1 bins per group.  With
+    a HIP device the table comes from csa_group_hist_async (on ``stream``, default the panels' current
+    stream; one host copy of the table and the status); without one, from ``group_hist_host``.  A
+    panel holding more than k members of a group raises CsaError(CSA_E_INVALID) on either path."""
+    k, G, W = int(k), len(groups), groups.W
+    bins = k + 1
+    on_device = _is_device_tensor(panels)
+    if not on_device:
+        panels = np.ascontiguousarray(panels, np.uint64).reshape(-1, W)
+        try:
+            import torch
+            have = torch.cuda.is_available()
+        except ImportError:
+            have = False
+        if not have:
+            return CompositionHistogram(groups.labels, group_hist_host(groups.masks, panels, bins), len(panels), k)
+    import torch
+    dev = panels.device if on_device else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        st = stream or torch.cuda.current_stream(dev)
+        with torch.cuda.stream(st):
+            if not on_device:
+                panels = torch.from_numpy(panels.view(np.int64).reshape(-1)).to(dev)
+            if panels.numel() % W:
+                raise ValueError("panels: %d words are no whole number of W = %d" % (panels.numel(), W))
+            S = panels.numel() // W
+            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
+            out = torch.zeros(G * bins + 4, dtype=torch.int64, device=dev)
+            status = torch.zeros(4, dtype=torch.int32, device=dev)
+            group_hist_device(panels, S, W, d_masks, G, bins, out, status, st)
+            out[G * bins:].copy_(status)
+            h = out.cpu().numpy()                      # the call's one host wait
+    words = (h[G * bins:] & 0xFFFFFFFF).astype(np.uint32)
+    if words[0]:
+        N.check(N.lib().csa_status_decode(N.ptr(words)))
+    return CompositionHistogram(groups.labels, h[:G * bins].reshape(G, bins).copy(), S, k)
+
+
+INTERSECTION_SHARES = ("population share", "panel share LEGACY", "panel share LEXIMIN", "pool share", "quota share")
+# analysis.py:509-512, in the reference's order
+INTERSECTION_DIFF_PAIRS = (("panel share LEXIMIN", "population share"), ("panel share LEGACY", "population share"),
+                           ("panel share LEXIMIN", "pool share"), ("panel share LEGACY", "pool share"),
+                           ("panel share LEXIMIN", "quota share"), ("panel share LEGACY", "quota share"),
+                           ("panel share LEXIMIN", "panel share LEGACY"))
+
+
+def intersectional_representation(instance, legacy_alloc, leximin_alloc, intersections):
+    """The numbers of plot_intersectional_representation (analysis.py:474-530), without the plot.
+
+    ``intersections``: a path to an ``intersections.csv``-shaped table, or rows
+    ``((c1, f1), (c2, f2), population share)``.  Returns ``(table, errors)``: ``table`` maps
+    "labels" to the ((c1, f1), (c2, f2)) pairs and each of INTERSECTION_SHARES to a float64 array in row
+    order; ``errors`` maps the reference's seven (share 1, share 2) keys, in its order, to the mean
+    squared difference.  The panel shares are the reference's float sums: the members' probabilities
+    added in the allocation's own order from 0, divided by k.  A path that does not exist returns
+    None, as the reference does; an unknown category or feature raises KeyError."""
+    import os
+    if isinstance(intersections, (str, os.PathLike)):
+        if not os.path.exists(intersections):
+            return None
+        intersections = read_intersections(intersections)
+    rows = [(tuple(a), tuple(b), float(share)) for a, b, share in intersections]
+    enc = _encoding(instance)
+    index = _feature_index(enc)
+    member = _feature_membership(enc)
+    pos = {aid: p for p, aid in enumerate(enc.agent_ids)}
+    k, n = instance.k, len(instance.agents)
+    allocs = []
+    for alloc in (legacy_alloc, leximin_alloc):
+        where = np.fromiter((pos[pers] for pers in alloc), np.int64, len(alloc))   # KeyError: not an agent
+        allocs.append((where, list(alloc.values())))
+    table = {name: np.zeros(len(rows), np.float64) for name in INTERSECTION_SHARES}
+    table["labels"] = [(a, b) for a, b, _ in rows]
+    for r, (a, b, share) in enumerate(rows):
+        both = member[index(a)] & member[index(b)]
+        table["population share"][r] = share
+        for name, (where, probs) in zip(("panel share LEGACY", "panel share LEXIMIN"), allocs):
+            table[name][r] = sum(probs[i] for i in np.flatnonzero(both[where]).tolist()) / k
+        table["pool share"][r] = int(both.sum()) / n
+        quota_share = 1
+        for category, feature in (a, b):
+            info = instance.categories[category][feature]
+            quota_share *= ((info["min"] + info["max"]) / 2) / k
+        table["quota share"][r] = quota_share
+    errors = {}
+    for s1, s2 in INTERSECTION_DIFF_PAIRS:
+        d = table[s1] - table[s2]
+        errors[(s1, s2)] = float(np.mean(d ** 2)) if len(rows) else float("nan")
+    return table, errors

@@ -420,6 +420,25 @@ int csa_portfolio_pairs_async(const uint64_t *d_xt, uint64_t n_panels, int32_t n
                               double *d_upper /* n(n-1)/2 or NULL */, double *d_alloc /* n or NULL */,
                               uint32_t flags, void *stream);
 
+/* Per-panel group composition: how many members of each agent group every panel holds, as one
+ * histogram per group (quota features: how often a feature sits on its minimum or maximum;
+ * two-feature intersections as in plot_intersectional_representation, analysis.py:459-530, which
+ * can only take their mean from the marginals; households; any agent set).
+ * hist[g*bins + c] += number of panels p in [0, n_panels) with popcount(panel_p & mask_g) == c.
+ * d_panels: n_panels*W (csa_draw_async layout); d_masks: n_groups*W, agent p = bit p & 63 of word
+ * p >> 6, padding bits zero; d_hist: n_groups*bins int64, ACCUMULATED (the caller zeroes it; chunks,
+ * calls and ranks add).  A panel whose count >= bins writes nothing for that group and sets
+ * CSA_E_INVALID (with the panel's index in this call) in d_status -- never a store outside d_hist;
+ * every other (panel, group) is still counted.
+ * Range: 1 <= W <= 8192 (one mask must fit 64 KB of LDS: CSA_E_UNSUPPORTED above, before any
+ * launch), every bins >= 1 (the per-workgroup LDS table holds up to 160 KB - masks, i.e. about 380 bins
+ * at W = 128; beyond that every count goes to d_hist directly, slower, same table), every
+ * n_groups >= 0, n_panels <= 2^46.  n_panels == 0 or n_groups == 0 is a no-op.  Stream-ordered, no
+ * host wait.  CSA_E_INVALID, before any device call, for W <= 0, n_groups < 0, bins < 1 or a NULL
+ * pointer with work to do (d_status is required). */
+int csa_group_hist_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W, const uint64_t *d_masks,
+                         int32_t n_groups, int32_t bins, int64_t *d_hist, uint32_t *d_status, void *stream);
+
 /* Decode a device status block (host copy of the 4 words) into a CSA_* code
  * and set csa_last_error() accordingly. */
 int csa_status_decode(const uint32_t *h_status);

@@ -9,8 +9,14 @@
       sf_e with an XMIN-sized portfolio (5n panels): end to end, upload and triangle read included,
       vs the host PairHistogram.add_portfolio_of_panels_to_histogram (median of 5, one process);
       and portfolio_pairs_kernel alone, there and at n = 8192, P = 5n
+  f3c group_hist_kernel (per-panel group composition, csrc/composition.inc) alone at sf_e (G = 377:
+      31 features + the 346 intersections of tests/golden/sf_e_110_intersections.csv) and at
+      synthetic8192 (G = its 40 features), 10^6 panels each, ms per launch next to the draw of the
+      same panels in the same run; analysis.legacy_composition against legacy_probabilities at sf_e
+      (median of 5, alternating, one process): the added ms; and the host numpy implementation over
+      10^5 of the same panels, for scale (its table checked equal to the device's over them)
 
-    python tools/bench_rows.py [--panels 1000000] [--rows f1,f2,f3,f3b]
+    python tools/bench_rows.py [--panels 1000000] [--rows f1,f2,f3,f3b,f3c]
 """
 import argparse
 import ctypes
@@ -115,6 +121,84 @@ def portfolio_row(P_, torch):
     return row
 
 
+def events_ms(torch, st, fn, reps):
+    """fn() enqueued reps times on stream st between two events, after one warm-up call: ms per call."""
+    fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(st)
+    for _ in range(reps):
+        fn()
+    e1.record(st)
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def composition_kernel(P_, torch, name, k, S, groups_of, host_panels=0):
+    """Draw S panels of the instance once, then time the draw and group_hist_kernel over them."""
+    N = importlib.import_module(PKG + "._native")
+    St = importlib.import_module(PKG + ".stats")
+    Dv = importlib.import_module(PKG + ".device")
+    inst = P_.read_instance(*paths(name), k)
+    enc = P_.encode(inst.categories, inst.agents)
+    groups = groups_of(inst)
+    G, W, bins = len(groups), enc.W, k + 1
+    pipe = Dv.DevicePipeline(enc, k, S, want_pairs=False, want_unique=False)
+    st = pipe.stream
+    draw_ms = events_ms(torch, st, lambda: pipe.draw(0, 0, S), 3)
+    pipe.check_status()
+    d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).cuda()
+    hist = torch.zeros(G * bins, dtype=torch.int64, device="cuda")
+    kernel_ms = events_ms(torch, st, lambda: St.group_hist_device(pipe.panels, S, W, d_masks, G, bins, hist,
+                                                                    pipe.status, st), 5)
+    pipe.check_status()
+    table = hist.cpu().numpy().reshape(G, bins)
+    row = {"instance": name, "n": enc.n, "W": W, "k": k, "groups": G, "bins": bins, "panels": S,
+           "draw_kernel": pipe.draw_kernel_name(), "draw_ms": draw_ms, "group_hist_kernel_ms": kernel_ms,
+           "rows_sum_to_launches_x_panels": bool(np.all(table.sum(axis=1) == 6 * S))}
+    if host_panels:
+        m = min(S, host_panels)
+        head = pipe.panels[:m * W].cpu().numpy().view(np.uint64).reshape(m, W)
+        t = time.perf_counter()
+        want = St.group_hist_host(groups.masks, head, bins)
+        row["host_numpy_panels"], row["host_numpy_ms"] = m, (time.perf_counter() - t) * 1e3
+        hist.zero_()
+        St.group_hist_device(pipe.panels, m, W, d_masks, G, bins, hist, pipe.status, st)
+        pipe.check_status()
+        row["device_equals_host_over_them"] = bool(np.array_equal(hist.cpu().numpy().reshape(G, bins), want))
+    return row
+
+
+def composition_row(P_, torch, S):
+    A = importlib.import_module(PKG + ".analysis")
+    St = importlib.import_module(PKG + ".stats")
+    fixture = os.path.join(REPO, "tests", "golden", "sf_e_110_intersections.csv")
+    both = lambda inst: St.feature_groups(inst) + St.intersection_groups(inst, fixture)
+    row = {"kernel_sf_e": composition_kernel(P_, torch, "sf_e_110", 110, S, both, host_panels=10 ** 5),
+           "kernel_synthetic8192": composition_kernel(P_, torch, "synthetic8192_200", 200, S, St.feature_groups),
+           "estimate": "derived before the kernel existed, VALU-bound at sf_e: about 1 ms per 10^6 panels "
+                       "(4W + 4 wave instructions per panel and 64-group slab, 6 slabs)"}
+    inst = P_.read_instance(*paths("sf_e_110"), 110)
+    groups = both(inst)
+    calls = {"legacy_probabilities": lambda: A.legacy_probabilities(inst, S, 1, keep_panels=False),
+             "legacy_composition": lambda: A.legacy_composition(inst, S, 1, groups, keep_panels=False)}
+    times = {name: [] for name in calls}
+    for name, fn in calls.items():                     # warm-up: encode, pipeline buffers, allocator
+        fn()
+    for _ in range(5):                                  # alternating, so both see the same machine
+        for name, fn in calls.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t) * 1e3)
+    med = {name: sorted(ts)[2] for name, ts in times.items()}
+    row["api_sf_e"] = {"panels": S, "groups": len(groups), "median_of": 5,
+                       "legacy_probabilities_ms": med["legacy_probabilities"],
+                       "legacy_composition_ms": med["legacy_composition"],
+                       "added_ms": med["legacy_composition"] - med["legacy_probabilities"],
+                       "all_ms": times}
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--panels", type=int, default=10 ** 6)
@@ -133,6 +217,8 @@ def main():
     out = {}
     if "f3b" in rows:
         out["f3b_portfolio"] = portfolio_row(P, torch)
+    if "f3c" in rows:
+        out["f3c_composition"] = composition_row(P, torch, args.panels)
     if not rows & {"f1", "f2", "f3"}:
         print(json.dumps(out))
         return
