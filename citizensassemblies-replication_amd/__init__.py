@@ -19,7 +19,12 @@ plus what a run's panels look like as a whole: legacy_composition(instance, iter
 returns legacy_probabilities' results and a CompositionHistogram (per agent group -- feature_groups,
 intersection_groups, agent_groups -- how many panels hold 0, 1, ..., k of its members), counted on the
 device by group_hist_kernel; intersectional_representation gives the numbers of
-plot_intersectional_representation (analysis.py:459-530)
+plot_intersectional_representation (analysis.py:459-530); and the same question for a LEXIMIN / XMIN
+portfolio: leximin_composition, xmin_composition, portfolio_composition return the probabilities'
+results and a WeightedCompositionHistogram (per group, the summed probability of the panels holding 0,
+1, ..., k members, added in portfolio order on the device by whist_count_kernel + whist_sum_kernel, bit
+for bit what group_whist_host adds on the host); composition_difference sets two compositions against
+each other (LEGACY against LEXIMIN)
 
 plus xmin._get_panel_not_in_portfolio_if_possible (XMIN's LEGACY caller,
 xmin.py:464-474) on the device.
@@ -29,12 +34,17 @@ from .legacy import SelectionError, check_min_cats, find_random_sample_legacy, s
 from .analysis import PairHistogram, PanelSet, legacy_find, legacy_find_batch, legacy_probabilities  # noqa: F401
 from .analysis import leximin_probabilities, portfolio_probabilities, xmin_probabilities  # noqa: F401
 from .analysis import legacy_composition  # noqa: F401
+from .analysis import leximin_composition, portfolio_composition, xmin_composition  # noqa: F401
 from .stats import (CompositionHistogram, GroupSet, agent_groups, feature_groups, group_composition,  # noqa: F401
                     intersection_groups, intersectional_representation)
+from .stats import (WeightedCompositionHistogram, composition_difference, group_whist_host,  # noqa: F401
+                    portfolio_group_composition)
 from . import _native, xmin  # noqa: F401
 
 __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_cats",
            "find_random_sample_legacy", "seed", "set_rng_mode", "PairHistogram", "PanelSet", "legacy_find",
            "legacy_find_batch", "legacy_probabilities", "leximin_probabilities", "xmin_probabilities",
            "portfolio_probabilities", "legacy_composition", "CompositionHistogram", "GroupSet", "agent_groups",
-           "feature_groups", "group_composition", "intersection_groups", "intersectional_representation"]
+           "feature_groups", "group_composition", "intersection_groups", "intersectional_representation",
+           "leximin_composition", "xmin_composition", "portfolio_composition", "WeightedCompositionHistogram",
+           "composition_difference", "group_whist_host", "portfolio_group_composition"]

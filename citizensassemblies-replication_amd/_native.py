@@ -37,6 +37,7 @@ CSA_PAIR_ALONE = 0x400      # engine hint: nothing runs beside the launch (the k
 CSA_DRAW_RESET_STATUS = 0x1  # csa_draw_xt_async flags: zero the status words, and the draw statistics,
 CSA_DRAW_RESET_STATS = 0x2   # on the stream before the draw
 CSA_PORTFOLIO_ACCUMULATE = 0x1  # csa_portfolio_pairs_async: add onto the stored values
+CSA_GROUP_WHIST_ACCUMULATE = 0x1  # csa_group_whist_async: add onto the stored table
 
 # every symbol include/csa_legacy.h declares, with its ctypes signature
 _P = ctypes.c_void_p
@@ -84,6 +85,9 @@ SIGNATURES = {
     "csa_pairs_diag_async": (ctypes.c_int, [_P, _I32, _P, _P]),
     "csa_portfolio_pairs_async": (ctypes.c_int, [_P, _U64, _I32, _P, _P, _P, _U32, _P]),
     "csa_group_hist_async": (ctypes.c_int, [_P, _U64, _I32, _P, _I32, _I32, _P, _P, _P]),
+    "csa_group_whist_scratch_bytes": (_U64, [_U64, _I32]),
+    "csa_group_whist_scratch": (ctypes.c_int, [_P, _U64]),
+    "csa_group_whist_async": (ctypes.c_int, [_P, _U64, _I32, _P, _P, _I32, _I32, _P, _U32, _P, _P]),
     "csa_draw_xt_async": (ctypes.c_int, [_P, _I32, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P, _P, _U32, _P]),
     "csa_status_decode": (ctypes.c_int, [_P]),
     "csa_legacy_draw_mt": (ctypes.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _U64, _U32,
@@ -113,7 +117,8 @@ class CsaError(RuntimeError):
 def build(verbose=False):
     """Compile csrc/csa_legacy.hip for gfx950 into LIB_PATH (in-tree)."""
     # no -ffast-math, and none may be added: portfolio_pairs_kernel's float64 sums are the reference's
-    # only while the compiler keeps every addition in program order (csrc/portfolio.inc)
+    # only while the compiler keeps every addition in program order (csrc/portfolio.inc), and so are
+    # whist_sum_kernel's (csrc/portfolio_composition.inc)
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
            "-o", LIB_PATH, SRC, SRC_MT]
     if verbose:

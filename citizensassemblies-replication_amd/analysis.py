@@ -21,6 +21,10 @@ Kept names and semantics (reference file:line):
                                        transpose, and portfolio_pairs_kernel, which sums every
                                        pair's and person's probabilities in portfolio order in
                                        float64, so the values are the reference's bit for bit.
+  * ``leximin_composition``,           new: the same calls with a fourth result, the weighted group
+    ``xmin_composition``,              composition of the portfolio (stats.WeightedCompositionHistogram) from
+    ``portfolio_composition``          whist_count_kernel + whist_sum_kernel over the same upload -- float64
+                                       sums in portfolio order, bit for bit stats.group_whist_host's.
 The LEXIMIN / XMIN solvers (Gurobi) and the plotting code stay in the reference (CPU).
 """
 import ctypes
@@ -750,14 +754,15 @@ def _portfolio_launch(rows, weights, n, d_upper, d_alloc, accumulate=False):
     """Upload the packed rows and the weights, transpose (csa_transpose_count_async) and run
     portfolio_pairs_kernel into ``d_upper`` / ``d_alloc`` (device float64 tensors or None), all on the
     outputs' device and its current stream.  Nothing waits for the kernels: the caller reads what it
-    needs."""
+    needs.  Returns the uploaded ``(rows, weights)`` device tensors (None, None without panels), for a
+    caller that runs a second kernel over the same upload."""
     import torch
     L = N.lib()
     P = len(weights) if n else 0
     dev = (d_upper if d_upper is not None else d_alloc).device
     with torch.cuda.device(dev):
         sp = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        xt = w = None
+        xt = w = d_rows = None
         if P:
             d_rows = torch.from_numpy(rows.view(np.int64).reshape(-1)).to(dev)
             w = torch.from_numpy(np.ascontiguousarray(weights, np.float64)).to(dev)
@@ -766,6 +771,7 @@ def _portfolio_launch(rows, weights, n, d_upper, d_alloc, accumulate=False):
             N.check(L.csa_transpose_count_async(N.ptr(d_rows), P, n, N.ptr(xt), N.ptr(cnt), sp))
         N.check(L.csa_portfolio_pairs_async(N.ptr(xt), P, n, N.ptr(w), N.ptr(d_upper), N.ptr(d_alloc),
                                             N.CSA_PORTFOLIO_ACCUMULATE if accumulate else 0, sp))
+    return d_rows, w
 
 
 def portfolio_probabilities(instance: Instance, portfolio, probabilities, min_probability=None):
@@ -788,6 +794,14 @@ def portfolio_probabilities(instance: Instance, portfolio, probabilities, min_pr
     ``selection_probs[agent_id] +=`` does there.  Only the packed panels and the weights are
     uploaded; only ``alloc`` and, on first access, the triangle are read back.  Both results are the
     reference's float64 values bit for bit (csa_portfolio_pairs_async's summation-order contract)."""
+    return _portfolio_run(instance, portfolio, probabilities, min_probability, None)[:3]
+
+
+def _portfolio_run(instance, portfolio, probabilities, min_probability, groups):
+    """portfolio_probabilities' body; with ``groups`` (a stats.GroupSet) the packed rows and weights it
+    uploaded also go through csa_group_whist_async, whose float64[G, k + 1] table and status come back
+    in the same host copy as ``alloc``.  Returns (alloc, panels, pair_histogram,
+    WeightedCompositionHistogram or None)."""
     import torch
     enc = encode_cached(instance.categories, instance.agents)
     ids, n = enc.agent_ids, enc.n
@@ -798,16 +812,66 @@ def portfolio_probabilities(instance: Instance, portfolio, probabilities, min_pr
     x, rows = _membership([panel for panel, _ in pairs], n, pos.__getitem__)   # KeyError: agent not in the instance
     weights = np.array([pob for _, pob in pairs], np.float64).reshape(-1)
     m = n * (n - 1) // 2
+    G, bins = (len(groups), int(instance.k) + 1) if groups is not None else (0, 0)
     tri = torch.empty(max(m, 1), dtype=torch.float64, device="cuda")
-    d_alloc = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")
-    _portfolio_launch(rows, weights, n, tri, d_alloc)
+    # alloc, then the composition table and its status words: one tensor, one host copy
+    out = torch.empty(max(n, 1) + (G * bins + 2 if groups is not None else 0), dtype=torch.float64, device="cuda")
+    d_alloc = out[:max(n, 1)]
+    d_rows, d_w = _portfolio_launch(rows, weights, n, tri, d_alloc)
+    if groups is not None:
+        from . import stats as St
+        dev = out.device
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            table, status = out[max(n, 1):max(n, 1) + G * bins], out[max(n, 1) + G * bins:].view(torch.int32)
+            status.zero_()
+            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
+            St.group_whist_device(d_rows, len(weights) if n else 0, enc.W, d_w, d_masks, G, bins, table, status, st)
     # the panel set while the device works: members in ascending position (np.nonzero walks row-major)
     names = list(map(ids.__getitem__, np.nonzero(x)[1].tolist()))
     ends = np.cumsum(np.count_nonzero(x, axis=1)).tolist()
     panels = {tuple(names[a:b]) for a, b, (_, pob) in zip([0] + ends[:-1], ends, pairs)
               if min_probability is None or pob > min_probability}
-    alloc = dict(zip(ids, d_alloc[:n].cpu().numpy().tolist()))          # the call's one host wait
-    return alloc, panels, PairHistogram._from_device_triangle(n, tri)
+    total = St.portfolio_total(weights) if groups is not None else None
+    h = out.cpu().numpy()                                                # the call's one host wait
+    alloc = dict(zip(ids, h[:n].tolist()))
+    comp = None
+    if groups is not None:
+        words = h[max(n, 1) + G * bins:].view(np.uint32)
+        if words[0]:
+            N.check(N.lib().csa_status_decode(N.ptr(np.ascontiguousarray(words))))
+        comp = St.WeightedCompositionHistogram(groups.labels, h[max(n, 1):max(n, 1) + G * bins].reshape(G, bins).copy(),
+                                               total, len(weights), instance.k)
+    return alloc, panels, PairHistogram._from_device_triangle(n, tri), comp
+
+
+def _check_groups(instance, groups):
+    """TypeError unless ``groups`` is a stats.GroupSet, ValueError unless it is over the instance's encoding
+    -- before a solver runs or anything is uploaded."""
+    from .stats import GroupSet
+    if not isinstance(groups, GroupSet):
+        raise TypeError("groups must be a stats.GroupSet")
+    W = max((len(instance.agents) + 63) // 64, 1)
+    if groups.W != W:
+        raise ValueError("groups of another encoding: W = %d, the instance has %d" % (groups.W, W))
+
+
+def portfolio_composition(instance: Instance, portfolio, probabilities, groups, min_probability=None):
+    """``portfolio_probabilities`` plus what the portfolio's panels look like as a whole: returns
+    ``(alloc, panels, pair_histogram, composition)``.
+
+    The first three are what ``portfolio_probabilities(instance, portfolio, probabilities,
+    min_probability)`` returns, bit for bit.  ``composition`` is a
+    ``stats.WeightedCompositionHistogram`` over ``groups`` (a ``stats.GroupSet``: ``feature_groups``,
+    ``intersection_groups``, ``agent_groups``, or their sum): per group, the summed probability of the
+    panels holding 0, 1, ..., k of its members, each entry added in portfolio order
+    (csa_group_whist_async's contract, so ``stats.group_whist_host`` gives the same bits).  It covers
+    the whole portfolio whatever ``min_probability`` says, as ``alloc`` does.  The packed rows are
+    uploaded once and serve both kernels; the table comes back in the call's one host wait.
+    ``stats.composition_difference`` sets it against ``legacy_composition``'s.  ``groups`` that is
+    not a GroupSet raises TypeError, one of another encoding ValueError."""
+    _check_groups(instance, groups)
+    return _portfolio_run(instance, portfolio, probabilities, min_probability, groups)
 
 
 def _solver(module, name):
@@ -825,10 +889,12 @@ def _solver(module, name):
     return fn
 
 
-def _solved_probabilities(instance, find_distribution, min_probability):
+def _solved_probabilities(instance, find_distribution, min_probability, groups=None):
     columns_data = {agent_id: {} for agent_id in instance.agents}
     portfolio, output_probs, _ = find_distribution(instance.categories, instance.agents, columns_data, instance.k,
                                                    False, [])
+    if groups is not None:
+        return portfolio_composition(instance, portfolio, output_probs, groups, min_probability=min_probability)
     return portfolio_probabilities(instance, portfolio, output_probs, min_probability=min_probability)
 
 
@@ -848,3 +914,22 @@ def xmin_probabilities(instance: Instance, find_distribution=None) -> Tuple[Prob
     if find_distribution is None:
         find_distribution = _solver("xmin", "find_distribution_xmin")
     return _solved_probabilities(instance, find_distribution, None)
+
+
+def leximin_composition(instance: Instance, groups, find_distribution=None):
+    """``leximin_probabilities`` plus the weighted composition of the LEXIMIN portfolio over ``groups``:
+    ``(alloc, panels, pair_histogram, composition)`` (see ``portfolio_composition``).  The solver is passed
+    or found as there.  The ``1e-11`` threshold applies to the returned panel set only: the composition
+    covers the whole portfolio, as the marginals do."""
+    _check_groups(instance, groups)
+    if find_distribution is None:
+        find_distribution = _solver("leximin", "find_distribution_leximin")
+    return _solved_probabilities(instance, find_distribution, 0.00000000001, groups)
+
+
+def xmin_composition(instance: Instance, groups, find_distribution=None):
+    """The same for XMIN (default solver: the reference's ``xmin.find_distribution_xmin``)."""
+    _check_groups(instance, groups)
+    if find_distribution is None:
+        find_distribution = _solver("xmin", "find_distribution_xmin")
+    return _solved_probabilities(instance, find_distribution, None, groups)

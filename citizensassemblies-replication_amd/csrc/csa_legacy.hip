@@ -16,7 +16,9 @@
 //   unique_kernel        open-addressing table of panel indices keyed by a 128-bit panel
 //                        hash, exact full-bitmask compare (found_panels, analysis.py:171,186).
 // and, for the LEXIMIN / XMIN analysis side (analysis.py:194-228), portfolio_pairs_kernel
-// (portfolio.inc): float64 sums of panel probabilities per pair and person, in portfolio order.
+// (portfolio.inc): float64 sums of panel probabilities per pair and person, in portfolio order, and
+// whist_count_kernel + whist_sum_kernel (portfolio_composition.inc): the same ordered sums per group
+// and number of members held.
 // The C ABI is declared in include/csa_legacy.h.
 #include <hip/hip_runtime.h>
 
@@ -1748,6 +1750,7 @@ __global__ __launch_bounds__(256) void pair_histogram_lds_kernel(const int64_t *
 
 #include "portfolio.inc"
 #include "composition.inc"
+#include "portfolio_composition.inc"
 
 }  // namespace
 
@@ -2854,6 +2857,83 @@ int csa_group_hist_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W,
     hipLaunchKernelGGL(group_hist_kernel, dim3(nslab, (unsigned)ranges), dim3(kGhThreads), lds, (hipStream_t)stream,
                        d_panels, n_panels, (int)W, d_masks, (int)n_groups, (int)bins, slab, use_table ? 1 : 0,
                        reinterpret_cast<unsigned long long *>(d_hist), d_status);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+// Weighted group composition of a portfolio: whist_count_kernel + whist_sum_kernel (portfolio_composition.inc).
+// Every argument is checked on the host before any device call.
+static thread_local void *g_whist_scratch = nullptr;  // lent by csa_group_whist_scratch, never owned
+static thread_local uint64_t g_whist_scratch_bytes = 0;
+
+uint64_t csa_group_whist_scratch_bytes(uint64_t n_panels, int32_t n_groups) {
+    if (n_groups <= 0 || n_panels >= (1ull << 40)) return 0;
+    return n_panels * (uint64_t)n_groups * sizeof(uint32_t);
+}
+
+int csa_group_whist_scratch(void *d_scratch, uint64_t bytes) {
+    if (!d_scratch && bytes) return fail(CSA_E_INVALID, "group whist: invalid NULL scratch of %llu bytes", (unsigned long long)bytes);
+    g_whist_scratch = d_scratch;
+    g_whist_scratch_bytes = d_scratch ? bytes : 0;
+    return CSA_OK;
+}
+
+int csa_group_whist_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W, const double *d_weights,
+                          const uint64_t *d_masks, int32_t n_groups, int32_t bins, double *d_hist, uint32_t flags,
+                          uint32_t *d_status, void *stream) {
+    if (W < 1) return fail(CSA_E_INVALID, "group whist: invalid W = %d", W);
+    if (n_groups < 0) return fail(CSA_E_INVALID, "group whist: invalid n_groups = %d", n_groups);
+    if (bins < 1) return fail(CSA_E_INVALID, "group whist: invalid bins = %d", bins);
+    if (flags & ~CSA_GROUP_WHIST_ACCUMULATE) return fail(CSA_E_INVALID, "group whist: invalid flags 0x%x", flags);
+    const bool accumulate = (flags & CSA_GROUP_WHIST_ACCUMULATE) != 0;
+    if (n_groups == 0) return CSA_OK;
+    const size_t table_bytes = (size_t)n_groups * (size_t)bins * sizeof(double);
+    if (n_panels == 0) {  // nothing to add: the stored values stay, or a zero fill (+0.0 is all-zero bits)
+        if (accumulate) return CSA_OK;
+        if (!d_hist) return fail(CSA_E_INVALID, "group whist: invalid NULL d_hist");
+        HIPCHK(hipMemsetAsync(d_hist, 0, table_bytes, (hipStream_t)stream));
+        return CSA_OK;
+    }
+    if (!d_panels || !d_weights || !d_masks || !d_hist || !d_status)
+        return fail(CSA_E_INVALID, "group whist: invalid NULL d_panels, d_weights, d_masks, d_hist or d_status");
+    if (W > kGhMaxW)
+        return fail(CSA_E_UNSUPPORTED, "group whist: W = %d words; one group's mask must fit %d bytes of LDS (W <= %d)", W,
+                    kGhMaskBytes, kGhMaxW);
+    if (n_panels >= (1ull << 40))
+        return fail(CSA_E_UNSUPPORTED, "group whist: %llu panels in one call (fewer than 2^40)", (unsigned long long)n_panels);
+    const uint64_t need = csa_group_whist_scratch_bytes(n_panels, n_groups);
+    if (!g_whist_scratch || g_whist_scratch_bytes < need)
+        return fail(CSA_E_INVALID, "group whist: invalid scratch of %llu B < csa_group_whist_scratch_bytes = %llu B "
+                    "(lend one with csa_group_whist_scratch)", (unsigned long long)g_whist_scratch_bytes,
+                    (unsigned long long)need);
+    uint32_t *counts = static_cast<uint32_t *>(g_whist_scratch);
+    hipStream_t st = (hipStream_t)stream;
+
+    int slab = 64;
+    while (slab * W * 8 > kGhMaskBytes) slab >>= 1;
+    const unsigned nslab = ((unsigned)n_groups + slab - 1) / slab;
+    // panel ranges: about kWhTargetBlocks workgroups in all, none with fewer than two passes of its waves
+    uint64_t ranges = std::max<uint64_t>(1, kWhTargetBlocks / nslab);
+    ranges = std::min(ranges, (n_panels + 4 * kWhWaves - 1) / (4 * kWhWaves));
+    hipLaunchKernelGGL(whist_count_kernel, dim3(nslab, (unsigned)ranges), dim3(kWhThreads), (size_t)slab * W * 8, st,
+                       d_panels, n_panels, (int)W, d_masks, (int)n_groups, (int)bins, slab, counts, d_status);
+    HIPCHK(hipGetLastError());
+
+    // the ordered pass: the largest slab of groups whose float64 rows fit the LDS beside the staged weights
+    const size_t w_bytes = (size_t)kWhChunk * sizeof(double), one_row = (size_t)whist_row_stride(bins) * sizeof(double);
+    int gslab = kWhSlab;
+    while (gslab > 1 && w_bytes + gslab * one_row > (size_t)kGhLdsBytes) gslab >>= 1;
+    const bool rows_in_lds = w_bytes + gslab * one_row <= (size_t)kGhLdsBytes;
+    if (!rows_in_lds) gslab = kWhSlab;
+    const unsigned nsum = ((unsigned)n_groups + gslab - 1) / gslab;
+    if (rows_in_lds) {
+        hipLaunchKernelGGL(whist_sum_kernel<true>, dim3(nsum), dim3(kWhSlab), w_bytes + gslab * one_row, st, counts,
+                           n_panels, d_weights, (int)n_groups, (int)bins, gslab, accumulate ? 1 : 0, d_hist);
+    } else {  // the rows are d_hist itself
+        if (!accumulate) HIPCHK(hipMemsetAsync(d_hist, 0, table_bytes, st));
+        hipLaunchKernelGGL(whist_sum_kernel<false>, dim3(nsum), dim3(kWhSlab), w_bytes, st, counts, n_panels, d_weights,
+                           (int)n_groups, (int)bins, gslab, accumulate ? 1 : 0, d_hist);
+    }
     HIPCHK(hipGetLastError());
     return CSA_OK;
 }

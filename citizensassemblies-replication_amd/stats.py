@@ -103,7 +103,8 @@ def sorted_pair_probabilities(pair_histogram, device="cuda"):
 # word p >> 6, padding bits zero): a quota feature, a two-feature intersection
 # (plot_intersectional_representation, analysis.py:459-530), a household.  ``group_composition``
 # counts, per group, the panels that hold 0, 1, ..., k of its members -- group_hist_kernel
-# (csrc/composition.inc) on the device, the numpy implementation below without one.
+# (csrc/composition.inc) on the device, the numpy implementation below without one.  For a LEXIMIN /
+# XMIN portfolio, whose panels carry probabilities, ``portfolio_group_composition`` further down.
 
 class GroupSet:
     """``labels`` (list), ``masks`` uint64[G, W], ``sizes`` int64[G] (members per group).  ``a + b``
@@ -357,6 +358,195 @@ def group_composition(groups, panels, k, stream=None):
     if words[0]:
         N.check(N.lib().csa_status_decode(N.ptr(words)))
     return CompositionHistogram(groups.labels, h[:G * bins].reshape(G, bins).copy(), S, k)
+
+
+# ---- weighted composition: the same question for a LEXIMIN / XMIN portfolio ------------------------
+#
+# A portfolio's panels carry float64 probabilities, so hist[g][c] is a float64 sum, and float64 addition
+# does not associate.  csa_group_whist_async fixes the order (ascending panel index, one add each);
+# ``group_whist_host`` is that contract on the host and the yardstick the kernels are held to, bit for bit.
+
+def _group_counts(masks, panels):
+    """int64[P, G]: popcount(panel_p & mask_g), as ``group_hist_host`` counts (0/1 products, exact)."""
+    G, W = masks.shape
+    P = panels.shape[0]
+    assert 64 * W < 1 << 24
+    m = np.unpackbits(masks.view(np.uint8).reshape(G, -1), axis=1, bitorder="little").astype(np.float32)
+    out = np.empty((P, G), np.int64)
+    step = max(1, (1 << 24) // (64 * W))
+    for off in range(0, P, step):
+        x = np.unpackbits(panels[off:off + step].view(np.uint8).reshape(-1, 8 * W), axis=1, bitorder="little")
+        out[off:off + step] = (x.astype(np.float32) @ m.T).astype(np.int64)
+    return out
+
+
+def group_whist_host(masks, panels, weights, bins, out=None):
+    """csa_group_whist_async's contract on the host: float64[G, bins], hist[g][c] = the sum of weights[p]
+    over the panels with popcount(panel_p & mask_g) == c, from +0.0 (or, with ``out=``, onto the values
+    ``out`` holds: it is updated in place and returned), added in ASCENDING p, one float64 add each --
+    a loop over the panels, each scattering its weight to one entry per group.  A count >= bins
+    raises CsaError(CSA_E_INVALID) before anything is added, as the device's status block reports it."""
+    masks = np.ascontiguousarray(masks, np.uint64)
+    panels = np.ascontiguousarray(panels, np.uint64)
+    weights = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    G, W = masks.shape
+    P = panels.shape[0]
+    assert panels.ndim == 2 and (P == 0 or panels.shape[1] == W) and len(weights) == P
+    bins = int(bins)
+    if out is None:
+        out = np.zeros((G, bins), np.float64)
+    assert out.shape == (G, bins) and out.dtype == np.float64 and out.flags.c_contiguous
+    if G == 0 or P == 0:
+        return out
+    c = _group_counts(masks, panels)
+    bad = np.argwhere(c >= bins)
+    if len(bad):
+        raise N.CsaError(N.CSA_E_INVALID, "group whist: panel %d holds %d members of group %d, bins = %d"
+                         % (bad[0][0], c[bad[0][0], bad[0][1]], bad[0][1], bins))
+    where = c + np.arange(G, dtype=np.int64) * bins            # [P, G]: one entry per group, all distinct
+    flat = out.reshape(-1)
+    for p in range(P):
+        flat[where[p]] += weights[p]
+    return out
+
+
+class WeightedCompositionHistogram:
+    """``values[g][c]`` = summed weight of the portfolio's panels holding exactly c members of group g
+    (host float64[G, k+1], the raw table, each entry added in portfolio order), over ``P`` panels of
+    size ``k``; ``total`` is the portfolio-order sum of the weights from ``0.``.  The derived
+    quantities describe the distribution ``values / total`` and mean what CompositionHistogram's do.
+    Holds host arrays only, so it pickles and loads where no GPU is visible."""
+
+    def __init__(self, labels, values, total, P, k):
+        self.labels = list(labels)
+        self.values = np.ascontiguousarray(values, np.float64)
+        self.total, self.P, self.k = float(total), int(P), int(k)
+        assert self.values.shape == (len(self.labels), self.k + 1)
+
+    def __len__(self):
+        return len(self.labels)
+
+    def probabilities(self):
+        """P(the drawn panel holds c members), float64[G, k+1] = values / total."""
+        return self.values / self.total
+
+    def mean(self):
+        """Expected members on the panel (by linearity also the sum of the members' marginals)."""
+        return (self.values * np.arange(self.k + 1, dtype=np.float64)).sum(axis=1) / self.total
+
+    def panel_share(self):
+        """mean / k: the panel share plot_intersectional_representation reports."""
+        return self.mean() / self.k
+
+    def variance(self):
+        """Variance of the members on the panel under the portfolio's distribution."""
+        d = np.arange(self.k + 1, dtype=np.float64)[None, :] - self.mean()[:, None]
+        return (self.values * d * d).sum(axis=1) / self.total
+
+    def prob_absent(self):
+        """P(the drawn panel holds no member of the group)."""
+        return self.values[:, 0] / self.total
+
+    def support(self):
+        """(lowest, highest) bin of non-zero weight per group, int64[G] each; (-1, -1) where there is none."""
+        nz = self.values != 0
+        some = nz.any(axis=1)
+        lo = np.where(some, nz.argmax(axis=1), -1)
+        hi = np.where(some, self.k - nz[:, ::-1].argmax(axis=1), -1)
+        return lo.astype(np.int64), hi.astype(np.int64)
+
+
+def portfolio_total(weights):
+    """The portfolio-order sum of the weights from ``0.``, one float64 add each."""
+    total = 0.
+    for w in np.asarray(weights, np.float64).reshape(-1).tolist():
+        total += w
+    return total
+
+
+def group_whist_device(d_panels, P, W, d_weights, d_masks, G, bins, d_hist, d_status, stream, accumulate=False):
+    """Enqueue csa_group_whist_async on ``stream`` (a torch stream); nothing waits.  The count scratch is a
+    tensor allocated here on that stream and lent to the call; it goes back to torch's allocator, which
+    reuses it only for work ordered after this on the same stream."""
+    import torch
+    L = N.lib()
+    need = int(L.csa_group_whist_scratch_bytes(int(P), int(G)))
+    with torch.cuda.stream(stream):
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=d_hist.device)
+    N.check(L.csa_group_whist_scratch(N.ptr(scratch), need))
+    try:
+        N.check(L.csa_group_whist_async(N.ptr(d_panels), int(P), int(W), N.ptr(d_weights), N.ptr(d_masks), int(G),
+                                        int(bins), N.ptr(d_hist), N.CSA_GROUP_WHIST_ACCUMULATE if accumulate else 0,
+                                        N.ptr(d_status), ctypes.c_void_p(stream.cuda_stream)))
+    finally:
+        N.check(L.csa_group_whist_scratch(None, 0))
+
+
+def portfolio_group_composition(groups, panels, weights, k, stream=None):
+    """Weighted composition of a portfolio over ``groups``: ``panels`` are its packed rows (host
+    uint64[P, W], or a device tensor of P*W int64 / uint64 words), ``weights`` its P probabilities in
+    portfolio order.  Returns a WeightedCompositionHistogram with k + 1 bins per group.  With a HIP
+    device the table comes from csa_group_whist_async (on ``stream``, default the panels' current
+    stream; one host copy of the table and the status); without one, from ``group_whist_host`` -- the
+    same bits either way.  A panel holding more than k members of a group raises
+    CsaError(CSA_E_INVALID) on either path."""
+    k, G, W = int(k), len(groups), groups.W
+    bins = k + 1
+    weights = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    total = portfolio_total(weights)
+    on_device = _is_device_tensor(panels)
+    if not on_device:
+        panels = np.ascontiguousarray(panels, np.uint64).reshape(-1, W)
+        try:
+            import torch
+            have = torch.cuda.is_available()
+        except ImportError:
+            have = False
+        if not have:
+            if len(panels) != len(weights):
+                raise ValueError("%d panels with %d weights" % (len(panels), len(weights)))
+            return WeightedCompositionHistogram(groups.labels, group_whist_host(groups.masks, panels, weights, bins),
+                                                total, len(panels), k)
+    import torch
+    dev = panels.device if on_device else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        st = stream or torch.cuda.current_stream(dev)
+        with torch.cuda.stream(st):
+            if not on_device:
+                panels = torch.from_numpy(panels.view(np.int64).reshape(-1)).to(dev)
+            if panels.numel() % W:
+                raise ValueError("panels: %d words are no whole number of W = %d" % (panels.numel(), W))
+            P = panels.numel() // W
+            if P != len(weights):
+                raise ValueError("%d panels with %d weights" % (P, len(weights)))
+            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
+            d_w = torch.from_numpy(weights).to(dev)
+            out = torch.empty(G * bins + 2, dtype=torch.float64, device=dev)   # table, then the status words
+            status = out[G * bins:].view(torch.int32)
+            status.zero_()
+            group_whist_device(panels, P, W, d_w, d_masks, G, bins, out, status, st)
+            h = out.cpu().numpy()                      # the call's one host wait
+    words = h[G * bins:].view(np.uint32)
+    if words[0]:
+        N.check(N.lib().csa_status_decode(N.ptr(np.ascontiguousarray(words))))
+    return WeightedCompositionHistogram(groups.labels, h[:G * bins].reshape(G, bins).copy(), total, P, k)
+
+
+def composition_difference(a, b):
+    """Two compositions over equal labels and k (CompositionHistogram or WeightedCompositionHistogram,
+    either side: LEGACY against LEXIMIN, LEXIMIN against XMIN) compared group by group.  Returns a dict of
+    "labels" and three float64[G] arrays: "total_variation", half the L1 distance between the two
+    ``probabilities()`` rows; "mean" and "prob_absent", a's minus b's.  ValueError when the labels or
+    k differ."""
+    for h in (a, b):
+        if not isinstance(h, (CompositionHistogram, WeightedCompositionHistogram)):
+            raise ValueError("composition_difference takes two composition histograms")
+    if a.labels != b.labels or a.k != b.k:
+        raise ValueError("compositions over different groups or panel sizes")
+    return {"labels": list(a.labels),
+            "total_variation": 0.5 * np.abs(a.probabilities() - b.probabilities()).sum(axis=1),
+            "mean": a.mean() - b.mean(),
+            "prob_absent": a.prob_absent() - b.prob_absent()}
 
 
 INTERSECTION_SHARES = ("population share", "panel share LEGACY", "panel share LEXIMIN", "pool share", "quota share")

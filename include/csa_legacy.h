@@ -439,6 +439,39 @@ int csa_portfolio_pairs_async(const uint64_t *d_xt, uint64_t n_panels, int32_t n
 int csa_group_hist_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W, const uint64_t *d_masks,
                          int32_t n_groups, int32_t bins, int64_t *d_hist, uint32_t *d_status, void *stream);
 
+/* Weighted group composition of a portfolio (LEXIMIN / XMIN): csa_group_hist_async's table with each
+ * panel counted by its float64 weight, what LEGACY-versus-LEXIMIN comparisons at the panel level need
+ * (how often a quota sits on its minimum, how often an intersection is absent); the marginals cannot
+ * give it.  d_panels, d_masks, W, n_groups, bins as for csa_group_hist_async; d_weights: n_panels
+ * float64 in portfolio order; d_hist: n_groups*bins float64.
+ * Summation-order contract: hist[g*bins + c] starts from +0.0 -- with CSA_GROUP_WHIST_ACCUMULATE from
+ * the stored value -- and receives d_weights[p] for every panel p with
+ * popcount(panel_p & mask_g) == c, in ASCENDING p, one IEEE float64 addition each: no reassociation, no
+ * tree reduction, no atomics on the values, no multiply.  A host loop over the panels gives the same
+ * bits (stats.group_whist_host).  Without the flag every one of the n_groups*bins entries is written
+ * (+0.0 where no panel lands); with it, entries no panel reaches keep their stored bits (a -0.0 stays
+ * -0.0).  A panel whose count >= bins adds nothing for that group and sets CSA_E_INVALID (with the
+ * panel's index) in d_status -- never a store outside d_hist; every other entry is still exact.
+ * Scratch: the call runs two kernels, a parallel count pass (u32 counts[n_panels][n_groups]) and the
+ * ordered sums over them; the counts go to a device buffer the caller lends beforehand with
+ * csa_group_whist_scratch(d_scratch, bytes), bytes >= csa_group_whist_scratch_bytes(n_panels,
+ * n_groups).  The loan is per calling thread and lasts until the next csa_group_whist_scratch call
+ * (NULL, 0 ends it); the buffer must stay valid until the enqueued work has run, and calls that share
+ * one buffer must be ordered on one stream.  Nothing is allocated by the enqueue.
+ * Range: 1 <= W <= 8192 (CSA_E_UNSUPPORTED above, before any launch), every bins >= 1 (the rows sit in
+ * LDS: 64 groups per workgroup to 302 bins, fewer beyond, one to 19 454; past that the row is d_hist
+ * itself, same bits, slower),
+ * n_panels < 2^40.  Stream-ordered, no host wait.  CSA_E_INVALID, before any device call, for W < 1,
+ * bins < 1, n_groups < 0, unknown flag bits, a NULL pointer that is needed, or a scratch loan smaller
+ * than csa_group_whist_scratch_bytes.  n_groups == 0 is a no-op; n_panels == 0 is a no-op with the
+ * flag and sets the table to +0.0 without (only d_hist is needed then). */
+#define CSA_GROUP_WHIST_ACCUMULATE 0x1u
+uint64_t csa_group_whist_scratch_bytes(uint64_t n_panels, int32_t n_groups);
+int csa_group_whist_scratch(void *d_scratch, uint64_t bytes);
+int csa_group_whist_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W, const double *d_weights,
+                          const uint64_t *d_masks, int32_t n_groups, int32_t bins, double *d_hist,
+                          uint32_t flags, uint32_t *d_status, void *stream);
+
 /* Decode a device status block (host copy of the 4 words) into a CSA_* code
  * and set csa_last_error() accordingly. */
 int csa_status_decode(const uint32_t *h_status);

@@ -16,7 +16,13 @@
       (median of 5, alternating, one process): the added ms; and the host numpy implementation over
       10^5 of the same panels, for scale (its table checked equal to the device's over them)
 
-    python tools/bench_rows.py [--panels 1000000] [--rows f1,f2,f3,f3b,f3c]
+  f3d whist_count_kernel + whist_sum_kernel (weighted group composition of a portfolio,
+      csrc/portfolio_composition.inc) alone, events, best of 3 windows after a warm-up: sf_e with
+      P = 5n = 8635 drawn panels and G = 377, and synthetic8192 with P = 5n = 40 960 and its 40 features;
+      in the same run stats.group_whist_host on the same input (its table checked bit-equal to the
+      device's) and portfolio_pairs_kernel over the same portfolio, the yardstick to report against
+
+    python tools/bench_rows.py [--panels 1000000] [--rows f1,f2,f3,f3b,f3c,f3d]
 """
 import argparse
 import ctypes
@@ -199,6 +205,76 @@ def composition_row(P_, torch, S):
     return row
 
 
+def best_of(torch, st, fn, windows=3, reps=5):
+    """fn() enqueued reps times between two events, `windows` times after one warm-up call: the best
+    window's ms per call, and all of them."""
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(windows):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(reps):
+            fn()
+        e1.record(st)
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / reps)
+    return min(ms), ms
+
+
+def weighted_composition_kernel(P_, torch, name, k, groups_of):
+    """Draw P = 5n panels of the instance as the portfolio, then time csa_group_whist_async (both
+    kernels) over them, the host implementation, and portfolio_pairs_kernel over the same portfolio."""
+    A = importlib.import_module(PKG + ".analysis")
+    N = importlib.import_module(PKG + "._native")
+    St = importlib.import_module(PKG + ".stats")
+    Dv = importlib.import_module(PKG + ".device")
+    inst = P_.read_instance(*paths(name), k)
+    enc = P_.encode(inst.categories, inst.agents)
+    groups = groups_of(inst)
+    n, G, W, bins = enc.n, len(groups), enc.W, k + 1
+    P = 5 * n
+    pipe = Dv.DevicePipeline(enc, k, P, want_pairs=False, want_unique=False)
+    st = pipe.stream
+    pipe.draw(0, 0, P)
+    pipe.check_status()
+    weights = np.asarray(portfolio_weights(P), np.float64)
+    with torch.cuda.stream(st):
+        d_w = torch.from_numpy(weights).cuda()
+        d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).cuda()
+        hist = torch.empty(G * bins, dtype=torch.float64, device="cuda")
+        best, all_ms = best_of(torch, st, lambda: St.group_whist_device(pipe.panels, P, W, d_w, d_masks, G, bins, hist,
+                                                                         pipe.status, st))
+    pipe.check_status()
+    table = hist.cpu().numpy().reshape(G, bins)
+    rows = pipe.panels[:P * W].cpu().numpy().view(np.uint64).reshape(P, W)
+    t = time.perf_counter()
+    want = St.group_whist_host(groups.masks, rows, weights, bins)
+    host_ms = (time.perf_counter() - t) * 1e3
+    pairs_best, pairs_all = None, []
+    for _ in range(3):                                   # the same best-of-3 for the yardstick
+        pairs_all.append(portfolio_kernel_ms(A, N, torch, rows, weights, n, reps=5)["kernel_ms"])
+    pairs_best = min(pairs_all)
+    return {"instance": name, "n": n, "W": W, "k": k, "groups": G, "bins": bins, "panels": P,
+            "group_whist_ms": best, "group_whist_windows_ms": all_ms,
+            "scratch_bytes": int(N.lib().csa_group_whist_scratch_bytes(P, G)),
+            "group_whist_host_ms": host_ms,
+            "device_bit_equal_to_host": bool(np.array_equal(table.view(np.uint64), want.view(np.uint64))),
+            "portfolio_pairs_kernel_ms": pairs_best, "portfolio_pairs_windows_ms": pairs_all,
+            "composition_over_pairs": best / pairs_best}
+
+
+def weighted_composition_row(P_, torch):
+    St = importlib.import_module(PKG + ".stats")
+    fixture = os.path.join(REPO, "tests", "golden", "sf_e_110_intersections.csv")
+    both = lambda inst: St.feature_groups(inst) + St.intersection_groups(inst, fixture)
+    return {"kernel_sf_e": weighted_composition_kernel(P_, torch, "sf_e_110", 110, both),
+            "kernel_synthetic8192": weighted_composition_kernel(P_, torch, "synthetic8192_200", 200, St.feature_groups),
+            "note": "group_whist_ms: whist_count_kernel + whist_sum_kernel per csa_group_whist_async call, events, "
+                    "best of 3 windows of 5 calls after a warm-up call; the scratch is allocated per call from "
+                    "torch's caching allocator (a pool hit after the warm-up)"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--panels", type=int, default=10 ** 6)
@@ -219,6 +295,8 @@ def main():
         out["f3b_portfolio"] = portfolio_row(P, torch)
     if "f3c" in rows:
         out["f3c_composition"] = composition_row(P, torch, args.panels)
+    if "f3d" in rows:
+        out["f3d_weighted_composition"] = weighted_composition_row(P, torch)
     if not rows & {"f1", "f2", "f3"}:
         print(json.dumps(out))
         return
