@@ -643,7 +643,8 @@ def test_distributed_draw_error_outranks_exchange_error(gpu_available, tmp_path)
 def test_unique_partitioned_matches_oracle(gpu_available, name, k, S):
     """csa_unique_async at sizes that take the partitioned path (duplicate-heavy couples / rejecty:
     a few hundred distinct panels; sf_e: all distinct) == the C oracle's exact count, and == the
-    single-table path (CSA_UNIQUE_PART=0)."""
+    single-table path (CSA_UNIQUE_PART=0).
+    The paths honest draws do not reach (n > 2^20, segments, full tables): tests/test_gpu_distinct.py."""
     import os
     A = pkg("analysis")
     inst, enc = _enc(name, k)
