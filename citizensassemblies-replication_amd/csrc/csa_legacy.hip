@@ -1845,142 +1845,6 @@ int check_k(const csa_instance *I, int32_t k) {
     return CSA_OK;
 }
 
-struct DrawConfig {
-    int G = 16, FPL = 1, WPL = 1;
-    bool lane = false;  // draw_lane_kernel (2 lanes per panel): FPL / WPL hold its FN / WN
-    bool wide = false;  // draw_wide_kernel (8 lanes per panel)
-    bool solo = false;  // draw_solo_kernel (1 lane per panel): FPL / WPL hold its FN / WN
-    bool k8 = false;    // lane / solo: the 8-bit need keys carrying their index (csa_instance::need8)
-    int np = 8;         // lane / solo (FN >= 16): slack bit planes, csa_instance::max_slack < 2^np
-    const void *fn = nullptr;
-    bool picks() const { return lane || wide || solo; }  // pick-list kernels (picks_pack_kernel builds the panels)
-};
-
-template <int FPL>
-const void *wide_fn_w(int wpl) {
-    switch (wpl) {
-        case 4: return reinterpret_cast<const void *>(&draw_wide_kernel<8, FPL, 4>);
-        case 8: return reinterpret_cast<const void *>(&draw_wide_kernel<8, FPL, 8>);
-        case 16: return reinterpret_cast<const void *>(&draw_wide_kernel<8, FPL, 16>);
-        default: return nullptr;
-    }
-}
-
-const void *wide_fn(int fpl, int wpl) {
-    switch (fpl) {
-        case 2: return wide_fn_w<2>(wpl);
-        case 4: return wide_fn_w<4>(wpl);
-        case 5: return wide_fn_w<5>(wpl);
-        case 8: return wide_fn_w<8>(wpl);
-        default: return nullptr;
-    }
-}
-
-// holder-scan batch of the lane kernel: all of a lane's row words in one LDS round trip
-// (CSA_LANE_SKDIV > 1 splits them, trading a round trip for VGPRs)
-#ifndef CSA_LANE_SKDIV
-#define CSA_LANE_SKDIV 1
-#endif
-template <int FN, int WN, int NP, bool K8>
-const void *lane_fn_wn() {
-    constexpr int SK = (WN / 2 + CSA_LANE_SKDIV - 1) / CSA_LANE_SKDIV;
-    return reinterpret_cast<const void *>(&draw_lane_kernel<FN, WN, SK, NP, K8>);
-}
-
-template <int FN, int NP, bool K8>
-const void *lane_fn_w(int wn) {
-    switch (wn) {
-        case 4: return lane_fn_wn<FN, 4, NP, K8>();
-        case 8: return lane_fn_wn<FN, 8, NP, K8>();
-        case 16: return lane_fn_wn<FN, 16, NP, K8>();
-        case 28: return lane_fn_wn<FN, 28, NP, K8>();
-        case 32: return lane_fn_wn<FN, 32, NP, K8>();
-        default: return nullptr;
-    }
-}
-
-template <int FN, int NP, bool K8>
-const void *solo_fn_w(int wn) {
-    switch (wn) {
-        case 4: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 4, NP, K8>);
-        case 8: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 8, NP, K8>);
-        case 16: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 16, NP, K8>);
-        case 28: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 28, NP, K8>);
-        case 32: return reinterpret_cast<const void *>(&draw_solo_kernel<FN, 32, NP, K8>);
-        default: return nullptr;
-    }
-}
-
-// slack bit planes of the register kernels: the built plane counts, the smallest that holds max_slack
-int slack_planes(int max_slack) { return max_slack < 32 ? 5 : max_slack < 128 ? 7 : 8; }
-
-template <int FN, bool K8>
-const void *solo_fn_p(int wn, int np) {
-    if constexpr (FN < 16) {
-        return solo_fn_w<FN, 8, K8>(wn);  // no slack planes at FN = 8
-    } else {
-        switch (np) {
-            case 5: return solo_fn_w<FN, 5, K8>(wn);
-            case 7: return solo_fn_w<FN, 7, K8>(wn);
-            case 8: return solo_fn_w<FN, 8, K8>(wn);
-            default: return nullptr;
-        }
-    }
-}
-
-template <int FN, bool K8>
-const void *lane_fn_p(int wn, int np) {
-    switch (np) {
-        case 5: return lane_fn_w<FN, 5, K8>(wn);
-        case 7: return lane_fn_w<FN, 7, K8>(wn);
-        case 8: return lane_fn_w<FN, 8, K8>(wn);
-        default: return nullptr;
-    }
-}
-
-// k8: the 8-bit need keys with the feature index inside (csa_instance::need8; draw_lane.inc)
-const void *solo_fn(int fn_, int wn, bool k8, int np) {
-    switch (fn_) {
-        case 8: return k8 ? solo_fn_p<8, true>(wn, np) : solo_fn_p<8, false>(wn, np);
-        case 16: return k8 ? solo_fn_p<16, true>(wn, np) : solo_fn_p<16, false>(wn, np);
-        default: return nullptr;
-    }
-}
-
-const void *lane_fn(int fn_, int wn, bool k8, int np) {
-    switch (fn_) {
-        case 32: return k8 ? lane_fn_p<32, true>(wn, np) : lane_fn_p<32, false>(wn, np);
-        default: return nullptr;
-    }
-}
-
-template <int G, int FPL, int WPL, bool GEN>
-const void *draw_fn() {
-    return reinterpret_cast<const void *>(&draw_kernel<G, FPL, WPL, GEN>);
-}
-
-template <int G, int FPL, bool GEN>
-const void *draw_fn_w(int wpl) {
-    switch (wpl) {
-        case 1: return draw_fn<G, FPL, 1, GEN>();
-        case 2: return draw_fn<G, FPL, 2, GEN>();
-        case 4: return draw_fn<G, FPL, 4, GEN>();
-        case 8: if constexpr (G == 16) return draw_fn<G, FPL, 8, GEN>(); else return nullptr;
-        case 16: if constexpr (G == 16) return draw_fn<G, FPL, 16, GEN>(); else return nullptr;
-        default: return nullptr;
-    }
-}
-
-template <int G, bool GEN>
-const void *draw_fn_fw(int fpl, int wpl) {
-    switch (fpl) {
-        case 1: return draw_fn_w<G, 1, GEN>(wpl);
-        case 2: return draw_fn_w<G, 2, GEN>(wpl);
-        case 4: return draw_fn_w<G, 4, GEN>(wpl);
-        default: return nullptr;
-    }
-}
-
 int pow2_ceil_int(int x) {
     int p = 1;
     while (p < x) p <<= 1;
@@ -1989,94 +1853,11 @@ int pow2_ceil_int(int x) {
 
 // FN / WN of the register kernel an instance's shape takes (lane: 16 < F <= 32, solo: F <= 16); false
 // when neither is built for it
-bool reg_kernel_shape(const csa_instance *I, bool &lane, int &fn, int &wn) {
+bool reg_kernel_shape(const csa_instance *I, int &fn, int &wn) {
     if (I->F > 32 || I->W > 32 || !I->d_pmask) return false;
-    lane = I->F > 16;
     fn = std::max(8, pow2_ceil_int(I->F));
     wn = I->W <= 4 ? 4 : I->W <= 8 ? 8 : I->W <= 16 ? 16 : I->W <= 28 ? 28 : 32;
     return true;
-}
-
-// Batch draws: draw_solo_kernel (1 lane per panel) or draw_lane_kernel (2 lanes per panel, 32
-// panels per wavefront) when the instance fits -- F <= 32, W <= 32, no max = 0 < min feature, |min|, |selected| < 2^15 (16-bit packed
-// need / remaining) and no feature starting above max ("selected == max" is tested as
-// need <= min - max) -- else draw_kernel with G = 16 (F <= 64, W <= 256) or 64.  Pick-order /
-// single-attempt draws (general mode) use draw_kernel<64, ..., true>.  CSA_DRAW_KERNEL=solo|lane|wide|16|64
-// forces a batch kernel the instance fits (parity tests of every layout).
-int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
-    general = general || I->d_addr_next;  // same-address deletions: draw_kernel<64, ..., true> only
-    const bool reg_ok = I->F <= 32 && I->d_pmask && !I->zero_max_min && I->W <= 32 && I->max_abs < 32768 &&
-                        !I->sel_over_max && I->max_slack <= 255;
-    const bool lane_ok = reg_ok && I->F > 16;  // built for FN = 32 only
-    const bool wide_ok = I->F <= 64 && I->W <= 128 && !I->zero_max_min && I->max_abs < 32768 && !I->sel_over_max;
-    const bool g16_ok = I->F <= 64 && I->W <= 256;
-    // one lane per panel when a lane holds few features (F <= 16: 142 VGPRs at W = 32, 3 waves/SIMD;
-    // example_large_200 281 vs 252 M panels/s, example_small_20 2950 vs 2490); at F = 32 the state needs
-    // 165 VGPRs and the two-lane kernel's 4 waves/SIMD win (sf_e 262 vs 247)
-    const bool solo_ok = reg_ok && I->F <= 16;
-    int choice = general ? 64 : solo_ok ? 1 : lane_ok ? 2 : wide_ok ? 8 : g16_ok ? 16 : 64;
-    if (const char *e = getenv("CSA_DRAW_KERNEL")) {
-        // the register kernels are built for the shapes they win on only (solo F <= 16, lane F > 16)
-        if (!general && !strcmp(e, "solo") && solo_ok) choice = 1;
-        else if (!general && !strcmp(e, "lane") && lane_ok && !solo_ok) choice = 2;
-        else if (!general && !strcmp(e, "wide") && wide_ok) choice = 8;
-        else if (!general && !strcmp(e, "16") && g16_ok) choice = 16;
-        else if (!general && !strcmp(e, "64")) choice = 64;
-    }
-    c.G = choice;
-    if (choice == 1) {
-        c.solo = true;
-        bool lane_shape;
-        reg_kernel_shape(I, lane_shape, c.FPL, c.WPL);
-        c.k8 = I->need8;
-        c.np = c.FPL >= 16 ? slack_planes(I->max_slack) : 8;
-        c.fn = solo_fn(c.FPL, c.WPL, c.k8, c.np);
-        if (!c.fn) return fail(CSA_E_UNSUPPORTED, "no solo draw kernel for F=%d W=%d", I->F, I->W);
-        return CSA_OK;
-    }
-    if (choice == 8) {  // draw_wide_kernel: FPL in {2, 4, 5, 8}, WPL in {4, 8, 16}
-        const int fpl = (I->F + 7) / 8;
-        c.wide = true;
-        c.FPL = fpl <= 2 ? 2 : fpl <= 4 ? 4 : fpl <= 5 ? 5 : 8;
-        c.WPL = I->W <= 32 ? 4 : I->W <= 64 ? 8 : 16;
-        c.fn = wide_fn(c.FPL, c.WPL);
-        if (!c.fn) return fail(CSA_E_UNSUPPORTED, "no wide draw kernel for F=%d W=%d", I->F, I->W);
-        return CSA_OK;
-    }
-    if (choice == 2) {
-        c.lane = true;
-        bool lane_shape;
-        reg_kernel_shape(I, lane_shape, c.FPL, c.WPL);
-        c.k8 = I->need8;
-        c.np = slack_planes(I->max_slack);
-        c.fn = lane_fn(c.FPL, c.WPL, c.k8, c.np);
-        if (!c.fn) return fail(CSA_E_UNSUPPORTED, "no lane draw kernel for F=%d W=%d", I->F, I->W);
-        return CSA_OK;
-    }
-    c.FPL = pow2_ceil_int((I->F + c.G - 1) / c.G);
-    c.WPL = pow2_ceil_int(std::max(1, (I->W + c.G - 1) / c.G));
-    if (general)
-        c.fn = draw_fn_fw<64, true>(c.FPL, c.WPL);
-    else
-        c.fn = c.G == 16 ? draw_fn_fw<16, false>(c.FPL, c.WPL) : draw_fn_fw<64, false>(c.FPL, c.WPL);
-    if (!c.fn)
-        return fail(CSA_E_UNSUPPORTED, "no draw kernel for F=%d n=%d (G=%d needs FPL=%d WPL=%d)", I->F, I->n, c.G,
-                    c.FPL, c.WPL);
-    return CSA_OK;
-}
-
-// The instantiation a DrawConfig stands for, spelled as the profiler prints it (csa_draw_kernel_name,
-// csa_draw_kernel_list).  `general`: draw_kernel's GENERAL parameter.
-void draw_config_name(const DrawConfig &c, bool general, char *buf, size_t len) {
-    if (c.solo)
-        snprintf(buf, len, "draw_solo_kernel<%d, %d, %d, %s>", c.FPL, c.WPL, c.np, c.k8 ? "true" : "false");
-    else if (c.lane)
-        snprintf(buf, len, "draw_lane_kernel<%d, %d, %d, %d, %s>", c.FPL, c.WPL,
-                 (c.WPL / 2 + CSA_LANE_SKDIV - 1) / CSA_LANE_SKDIV, c.np, c.k8 ? "true" : "false");
-    else if (c.wide)
-        snprintf(buf, len, "draw_wide_kernel<%d, %d, %d>", c.G, c.FPL, c.WPL);
-    else
-        snprintf(buf, len, "draw_kernel<%d, %d, %d, %s>", c.G, c.FPL, c.WPL, general ? "true" : "false");
 }
 
 // The register kernels' attempt-start tables, built on the host from the instance and its start state
@@ -2085,9 +1866,9 @@ void draw_config_name(const DrawConfig &c, bool general, char *buf, size_t len) 
 // csa_instance_set_state changes the start state.  A feature with min = max = 0 is removed (zero rows,
 // no person-mask bit, need = remaining = 0, all-ones slack); padding features likewise.
 int draw_image_build(csa_instance *I) {
-    bool lane = false;
     int FN = 0, WN = 0;
-    if (!reg_kernel_shape(I, lane, FN, WN)) return CSA_OK;
+    if (!reg_kernel_shape(I, FN, WN)) return CSA_OK;
+    const bool lane = FN > 16;
     const int F = I->F, W = I->W, n = I->n, LS = WN + 1;
     const DrawImage L = draw_image_layout(lane, FN, WN, n);
     std::vector<uint32_t> img((size_t)2 * L.words, 0u);
@@ -2214,165 +1995,7 @@ int launch_pack(const uint16_t *d_picks, uint64_t n_panels, int k, int W, uint64
     return CSA_OK;
 }
 
-// d_picks_ext: the lane kernel's pick lists go to this caller buffer and are NOT packed (the caller
-// runs csa_picks_pack_async); otherwise to the instance scratch, packed here into d_panels
-int launch_draw(const csa_instance *I, int32_t k, uint64_t seed, uint64_t panel_begin, uint64_t n_panels,
-                uint32_t max_attempts, uint32_t attempt_base, int single, uint64_t *d_panels,
-                uint64_t *d_hashes, uint32_t *d_attempts, int32_t *d_picks, uint32_t *d_status,
-                int32_t *d_sel_out, int32_t *d_rem_out, uint64_t *d_present_out, hipStream_t stream,
-                uint16_t *d_picks_ext = nullptr, const uint64_t *d_panel_list = nullptr,
-                const unsigned long long *d_list_len = nullptr, uint32_t *d_xt = nullptr,
-                int32_t *xt_written = nullptr, bool count_stats = true) {
-    if (xt_written) *xt_written = 0;
-    if (d_panel_list) count_stats = false;  // (index-list re-draws are not new panels)
-    int rc = check_k(I, k);
-    if (rc) return rc;
-    if ((!d_panels && !d_picks_ext) || !d_status) return fail(CSA_E_INVALID, "d_panels and d_status are required");
-    if (n_panels == 0) return CSA_OK;
-    if (k == 0 && !single && !d_sel_out && !d_present_out) {
-        int rejected = 0;
-        for (int f = 0; f < I->F; ++f) rejected |= I->sel0[f] < I->fmin[f];
-        // draw statistics as the kernels keep them: accepted new panels only (an index-list re-draw of
-        // the multi-GPU owner passes its list capacity as n_panels and draws no new panel)
-        if (!rejected && count_stats) const_cast<csa_instance *>(I)->panels_drawn += n_panels;
-        if (!d_panels) {  // pick-list draw of k = 0: nothing to write but the attempts / status
-            hipLaunchKernelGGL(empty_panels_kernel, dim3((unsigned)((n_panels + 255) / 256)), dim3(256), 0, stream,
-                               n_panels, d_attempts, d_status, panel_begin, rejected);
-            HIPCHK(hipGetLastError());
-            return CSA_OK;
-        }
-        HIPCHK(hipMemsetAsync(d_panels, 0, n_panels * I->W * 8, stream));
-        hipLaunchKernelGGL(empty_panels_kernel, dim3((unsigned)((n_panels + 255) / 256)), dim3(256), 0, stream,
-                           n_panels, d_attempts, d_status, panel_begin, rejected);
-        HIPCHK(hipGetLastError());
-        if (d_hashes) {
-            hipLaunchKernelGGL(panel_hash_kernel, dim3((unsigned)((n_panels * 4 + 255) / 256)), dim3(256), 0, stream,
-                               d_panels, n_panels, I->W, d_hashes);
-            HIPCHK(hipGetLastError());
-        }
-        return CSA_OK;
-    }
-    DrawConfig cfg;
-    int rc2 = pick_draw_config(I, single || d_picks || d_sel_out || d_present_out || d_panel_list, cfg);
-    if (rc2) return rc2;
-    DrawArgs A;
-    A.featmask = I->d_featmask;
-    A.fmin = I->d_fmin;
-    A.fmax = I->d_fmax;
-    A.sel0 = I->d_sel0;
-    A.rem0 = I->d_rem0;
-    A.present0 = I->d_present0;
-    A.pmask = I->d_pmask;
-    A.addr_next = I->d_addr_next;
-    A.n = I->n;
-    A.F = I->F;
-    A.W = I->W;
-    A.Ws = I->Ws;
-    A.k = k;
-    A.max_attempts = max_attempts ? max_attempts : kDefaultMaxAttempts;
-    A.attempt_base = attempt_base;
-    A.single = single;
-    A.seed = seed;
-    A.panel_begin = panel_begin;
-    A.n_panels = n_panels;
-    A.panels = d_panels;
-    A.hashes = d_hashes;
-    A.attempts = d_attempts;
-    A.picks = d_picks;
-    A.picks16 = nullptr;
-    A.status = d_status;
-    // legacy_find-semantics draws are counted; single attempts (csa_legacy_attempt) are not
-    A.stats = (single || !count_stats) ? nullptr : I->d_stats;
-    A.panel_list = d_panel_list;   // an index list: draw_kernel GENERAL (pick_draw_config above)
-    A.n_panels_dev = d_list_len;
-    A.sel_out = d_sel_out;
-    A.rem_out = d_rem_out;
-    A.present_out = d_present_out;
-    A.xt = nullptr;
-    A.npad = ((I->n + 255) / 256) * 256;  // csa_xt_pad
-    A.image = I->d_image;
-    if ((cfg.lane || cfg.solo) && !A.image) return fail(CSA_E_INVALID, "the instance has no draw image");
-    if (d_picks_ext && !cfg.picks()) return fail(CSA_E_UNSUPPORTED, "this instance does not take the pick-list draw");
-    csa_instance *M = const_cast<csa_instance *>(I);  // the lane kernel's pick-list scratch
-    if (d_picks_ext)
-        A.picks16 = d_picks_ext;
-    // (the fused pack's chunked layout reserves whole workgroups of <= 256 panels)
-    else if (cfg.picks() && (rc = lane_picks(M, ((n_panels + 255) & ~255ull) * (uint64_t)((k + 7) & ~7), stream,
-                                             &A.picks16)))
-        return rc;
-    const int threads = cfg.lane   ? kLaneThreads
-                        : cfg.solo ? kSoloThreads
-                        : cfg.wide ? kWideThreads
-                                   : draw_threads(cfg.FPL, cfg.WPL);
-    const int groups_wg = threads / cfg.G;
-    const size_t lds = cfg.lane   ? lane_lds_bytes(cfg.FPL, cfg.WPL, I->n)
-                       : cfg.solo ? solo_lds_bytes(cfg.FPL, cfg.WPL, I->n)
-                       : cfg.wide ? wide_lds_bytes(cfg.G, cfg.FPL, cfg.WPL)
-                                  : draw_lds_bytes(cfg.G, cfg.FPL, cfg.WPL, I->W, k, groups_wg);
-    if (lds > 160 * 1024) return fail(CSA_E_UNSUPPORTED, "draw kernel needs %zu B of LDS", lds);
-    // CSA_DRAW_LDS_PAD (diagnostic A/B only): extra bytes of LDS per register-kernel workgroup, to price
-    // the occupancy an LDS-resident pick-list tile would cost (128 panels x kpad u16 = 28 KB at sf_e)
-    static const size_t lds_pad = [] {
-        const char *e = getenv("CSA_DRAW_LDS_PAD");
-        return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)0;
-    }();
-    const size_t lds_launch = (cfg.lane || cfg.solo || cfg.wide) && lds + lds_pad <= 160 * 1024 ? lds + lds_pad : lds;
-    const uint64_t want = (n_panels + groups_wg - 1) / groups_wg;
-    // the lane kernel: one workgroup per 128 panels, not persistent -- sf_e 10^6 panels: 4.47 ms vs
-    // 5.05 ms for a persistent grid, and retiring workgroups let a concurrent stream's kernels in.
-    // draw_kernel: one resident grid (its 66 KB of feature rows at n = 8192 load once per workgroup)
-    uint64_t grid = want;
-    if (!cfg.picks()) {
-        int per_cu = 0, cus = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cfg.fn, threads, lds));
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, I->device));
-        grid = std::min(want, (uint64_t)std::max(per_cu, 1) * (uint64_t)std::max(cus, 1));
-    }
-    // the lane kernel packs its own panels (one workgroup per 128 panels, so every workgroup knows
-    // its panel range); the wide kernel's pick lists are packed by picks_pack_kernel
-    const bool fused = (cfg.lane || cfg.solo) && !d_picks_ext && d_panels;
-    if ((cfg.lane || cfg.solo) && !fused) {
-        A.panels = nullptr;
-        A.hashes = nullptr;
-    }
-    if (d_xt && (cfg.lane || cfg.solo) && fused) {  // the register kernels' fused tail also writes XT
-        A.xt = d_xt;
-        if (xt_written) *xt_written = 1;
-    }
-    void *args[] = {&A};
-    HIPCHK(hipLaunchKernel(cfg.fn, dim3((unsigned)std::max<uint64_t>(1, grid)), dim3(threads), args, lds_launch, stream));
-    HIPCHK(hipGetLastError());
-    if (!single && count_stats) M->panels_drawn += n_panels;
-    if (cfg.picks() && !d_picks_ext) {  // pick lists -> packed panels (+ hashes)
-        if (!fused && (rc = launch_pack(A.picks16, n_panels, k, I->W, d_panels, d_hashes, stream))) return rc;
-        HIPCHK(hipEventRecord(M->picks_done, stream));
-        M->picks_pending = true;
-    }
-    return CSA_OK;
-}
-
-// panels one full round of the batch draw's resident workgroups covers (CUs x resident workgroups
-// per CU x panels per workgroup): a launch of a multiple of it ends without a part-empty last round
-int draw_round_panels(const csa_instance *I, int32_t k, uint64_t *out) {
-    *out = 0;
-    int rc = check_k(I, k);
-    if (rc) return rc;
-    DrawConfig cfg;
-    if ((rc = pick_draw_config(I, false, cfg))) return rc;
-    const int threads = cfg.lane   ? kLaneThreads
-                        : cfg.solo ? kSoloThreads
-                        : cfg.wide ? kWideThreads
-                                   : draw_threads(cfg.FPL, cfg.WPL);
-    const size_t lds = cfg.lane   ? lane_lds_bytes(cfg.FPL, cfg.WPL, I->n)
-                       : cfg.solo ? solo_lds_bytes(cfg.FPL, cfg.WPL, I->n)
-                       : cfg.wide ? wide_lds_bytes(cfg.G, cfg.FPL, cfg.WPL)
-                                  : draw_lds_bytes(cfg.G, cfg.FPL, cfg.WPL, I->W, k, threads / cfg.G);
-    int per_cu = 0, cus = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cfg.fn, threads, lds));
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, I->device));
-    *out = (uint64_t)std::max(per_cu, 1) * (uint64_t)std::max(cus, 1) * (uint64_t)(threads / cfg.G);
-    return CSA_OK;
-}
+#include "draw_dispatch.inc"
 
 int read_status(const uint32_t *d_status, hipStream_t stream, uint32_t *h) {
     HIPCHK(hipMemcpyAsync(h, d_status, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -2994,8 +2617,13 @@ int csa_draw_async(const csa_instance *I, int32_t k, uint64_t seed, uint64_t pan
                    uint32_t max_attempts, uint64_t *d_panels, uint64_t *d_hashes, uint32_t *d_attempts,
                    int32_t *d_picks, uint32_t *d_status, void *stream) {
     if (!I) return fail(CSA_E_INVALID, "null instance");
-    return launch_draw(I, k, seed, panel_begin, n_panels, max_attempts, 0, 0, d_panels, d_hashes, d_attempts,
-                       d_picks, d_status, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    DrawRequest rq;
+    rq.a.k = k, rq.a.seed = seed, rq.a.panel_begin = panel_begin, rq.a.n_panels = n_panels;
+    rq.a.max_attempts = max_attempts;
+    rq.a.panels = d_panels, rq.a.hashes = d_hashes, rq.a.attempts = d_attempts, rq.a.picks = d_picks;
+    rq.a.status = d_status;
+    rq.stream = (hipStream_t)stream;
+    return launch_draw(I, rq);
 }
 
 int csa_draw_xt_async(const csa_instance *I, int32_t k, uint64_t seed, uint64_t panel_begin, uint64_t n_panels,
@@ -3009,17 +2637,25 @@ int csa_draw_xt_async(const csa_instance *I, int32_t k, uint64_t seed, uint64_t 
         HIPCHK(hipMemsetAsync(M->d_stats, 0, 16, (hipStream_t)stream));
         M->panels_drawn = 0;
     }
-    return launch_draw(I, k, seed, panel_begin, n_panels, max_attempts, 0, 0, d_panels, d_hashes, d_attempts,
-                       nullptr, d_status, nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr,
-                       d_xt, xt_written);
+    DrawRequest rq;
+    rq.a.k = k, rq.a.seed = seed, rq.a.panel_begin = panel_begin, rq.a.n_panels = n_panels;
+    rq.a.max_attempts = max_attempts;
+    rq.a.panels = d_panels, rq.a.hashes = d_hashes, rq.a.attempts = d_attempts, rq.a.status = d_status;
+    rq.a.xt = d_xt, rq.xt_written = xt_written;
+    rq.stream = (hipStream_t)stream;
+    return launch_draw(I, rq);
 }
 
 int csa_redraw_async(const csa_instance *I, int32_t k, uint64_t seed, uint64_t panel_begin, uint64_t n_panels,
                      uint32_t max_attempts, uint64_t *d_panels, uint32_t *d_status, void *stream) {
     if (!I || !d_panels || !d_status) return fail(CSA_E_INVALID, "redraw: null instance, d_panels or d_status");
-    return launch_draw(I, k, seed, panel_begin, n_panels, max_attempts, 0, 0, d_panels, nullptr, nullptr, nullptr,
-                       d_status, nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, /*count_stats=*/false);
+    DrawRequest rq;
+    rq.a.k = k, rq.a.seed = seed, rq.a.panel_begin = panel_begin, rq.a.n_panels = n_panels;
+    rq.a.max_attempts = max_attempts;
+    rq.a.panels = d_panels, rq.a.status = d_status;
+    rq.stream = (hipStream_t)stream;
+    rq.count_stats = false;
+    return launch_draw(I, rq);
 }
 
 int32_t csa_picks_stride(int32_t k) { return (k + 7) & ~7; }
@@ -3034,8 +2670,12 @@ int csa_draw_picks_async(const csa_instance *I, int32_t k, uint64_t seed, uint64
                          uint32_t max_attempts, uint16_t *d_picks, uint32_t *d_attempts, uint32_t *d_status,
                          void *stream) {
     if (!I || !d_picks) return fail(CSA_E_INVALID, "draw_picks: null instance or d_picks");
-    return launch_draw(I, k, seed, panel_begin, n_panels, max_attempts, 0, 0, nullptr, nullptr, d_attempts, nullptr,
-                       d_status, nullptr, nullptr, nullptr, (hipStream_t)stream, d_picks);
+    DrawRequest rq;
+    rq.a.k = k, rq.a.seed = seed, rq.a.panel_begin = panel_begin, rq.a.n_panels = n_panels;
+    rq.a.max_attempts = max_attempts;
+    rq.a.picks16 = d_picks, rq.a.attempts = d_attempts, rq.a.status = d_status;
+    rq.stream = (hipStream_t)stream;
+    return launch_draw(I, rq);
 }
 
 int csa_picks_pack_async(const uint16_t *d_picks, uint64_t n_panels, int32_t k, int32_t n, uint64_t *d_panels,
@@ -3064,40 +2704,21 @@ int csa_draw_kernel_name(const csa_instance *I, int32_t k, char *buf, uint64_t l
     DrawConfig cfg;
     rc = pick_draw_config(I, false, cfg);
     if (rc) return rc;
-    draw_config_name(cfg, false, buf, (size_t)len);
+    // the name entry never reports GENERAL: an instance with address rings names the batch kernel
+    if (cfg.family == DrawFamily::g64_general) cfg.family = DrawFamily::g64;
+    draw_config_name(cfg, buf, (size_t)len);
     return CSA_OK;
 }
 
-// Every instantiation pick_draw_config can resolve, asked of the dispatch functions themselves: the
-// candidate ranges are wider than anything built, and a combination counts when its dispatcher
-// returns a kernel (solo at FN < 16 takes no plane count: pick_draw_config reports np = 8 there).
+// Every instantiation pick_draw_config can resolve: the rows of kDrawKernels (draw_dispatch.inc).
 int csa_draw_kernel_list(char *buf, uint64_t len) {
     std::string all;
     char name[128];
-    // choice: pick_draw_config's (1 solo, 2 lane, 8 wide, 16 / 64 draw_kernel)
-    auto add = [&](const void *fn, int choice, int fpl, int wpl, int np, bool k8, bool general) {
-        if (!fn) return;
-        DrawConfig c;
-        c.G = choice, c.FPL = fpl, c.WPL = wpl, c.np = np, c.k8 = k8;
-        c.solo = choice == 1, c.lane = choice == 2, c.wide = choice == 8;
-        draw_config_name(c, general, name, sizeof name);
+    for (const DrawConfig &c : kDrawKernels) {
+        draw_config_name(c, name, sizeof name);
         all += name;
         all += '\n';
-    };
-    for (int fn = 1; fn <= 64; ++fn)
-        for (int wn = 1; wn <= 64; ++wn)
-            for (int np = 1; np <= 8; ++np)
-                for (int k8 = 1; k8 >= 0; --k8) {
-                    if (fn >= 16 || np == 8) add(solo_fn(fn, wn, k8 != 0, np), 1, fn, wn, np, k8 != 0, false);
-                    add(lane_fn(fn, wn, k8 != 0, np), 2, fn, wn, np, k8 != 0, false);
-                }
-    for (int fpl = 1; fpl <= 16; ++fpl)
-        for (int wpl = 1; wpl <= 32; ++wpl) {
-            add(wide_fn(fpl, wpl), 8, fpl, wpl, 8, false, false);
-            add(draw_fn_fw<16, false>(fpl, wpl), 16, fpl, wpl, 8, false, false);
-            add(draw_fn_fw<64, false>(fpl, wpl), 64, fpl, wpl, 8, false, false);
-            add(draw_fn_fw<64, true>(fpl, wpl), 64, fpl, wpl, 8, false, true);
-        }
+    }
     if (!buf || len < all.size() + 1)
         return fail(CSA_E_INVALID, "draw kernel list: the buffer needs %zu bytes", all.size() + 1);
     memcpy(buf, all.c_str(), all.size() + 1);
@@ -3448,8 +3069,12 @@ int csa_unique_keys_async(const csa_instance *I, int32_t k, uint64_t seed, uint3
                        d_status);
     HIPCHK(hipGetLastError());
     // re-draw the listed panels (a persistent index-list draw: workgroups past the list leave at once)
-    int rc = launch_draw(I, k, seed, 0, 2 * total, max_attempts, 0, 0, rows, nullptr, nullptr, nullptr, d_status,
-                         nullptr, nullptr, nullptr, st, nullptr, list, list_len);
+    DrawRequest rq;
+    rq.a.k = k, rq.a.seed = seed, rq.a.n_panels = 2 * total, rq.a.max_attempts = max_attempts;
+    rq.a.panel_list = list, rq.a.n_panels_dev = list_len;
+    rq.a.panels = rows, rq.a.status = d_status;
+    rq.stream = st;
+    int rc = launch_draw(I, rq);
     if (rc) return rc;
     hipLaunchKernelGGL(key_verify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t *)rows,
                        W, (const unsigned long long *)list_len, table2, slots2 - 1,
@@ -3545,10 +3170,14 @@ static int sample_enqueue(csa_instance *I, int32_t k, uint64_t seed, uint64_t pa
         const uint64_t len = std::min(chunk, n_panels - off);
         uint64_t *cp = r.panels + off * W;
         // the draw also writes the panels' 128-bit hashes (picks_pack_kernel / draw_kernel)
-        if ((rc = launch_draw(I, k, seed, panel_begin + off, len, max_attempts, 0, 0, cp,
-                              r.hashes ? r.hashes + 2 * off : nullptr, r.attempts ? r.attempts + off : nullptr,
-                              nullptr, r.status, nullptr, nullptr, nullptr, sdraw)))
-            return rc;
+        DrawRequest rq;
+        rq.a.k = k, rq.a.seed = seed, rq.a.panel_begin = panel_begin + off, rq.a.n_panels = len;
+        rq.a.max_attempts = max_attempts;
+        rq.a.panels = cp, rq.a.status = r.status;
+        rq.a.hashes = r.hashes ? r.hashes + 2 * off : nullptr;
+        rq.a.attempts = r.attempts ? r.attempts + off : nullptr;
+        rq.stream = sdraw;
+        if ((rc = launch_draw(I, rq))) return rc;
         HIPCHK(hipEventRecord(I->drawn, sdraw));
         HIPCHK(hipStreamWaitEvent(spost, I->drawn, 0));
         if (r.counts && (rc = csa_transpose_count_async(cp, len, n, xt, r.counts, spost))) return rc;
@@ -3799,9 +3428,12 @@ int csa_first_panel_not_in(csa_instance *I, int32_t k, uint64_t seed, uint64_t p
         len = std::min(len, n_panels - done);
         HIPCHK(hipMemsetAsync(status, 0, 16, st));
         HIPCHK(hipMemsetAsync(first, 0xFF, 8, st));
-        if ((rc = launch_draw(I, k, seed, panel_begin + done, len, max_attempts, 0, 0, panels, hashes, nullptr,
-                              nullptr, status, nullptr, nullptr, nullptr, st)))
-            return rc;
+        DrawRequest rq;
+        rq.a.k = k, rq.a.seed = seed, rq.a.panel_begin = panel_begin + done, rq.a.n_panels = len;
+        rq.a.max_attempts = max_attempts;
+        rq.a.panels = panels, rq.a.hashes = hashes, rq.a.status = status;
+        rq.stream = st;
+        if ((rc = launch_draw(I, rq))) return rc;
         hipLaunchKernelGGL(member_scan_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, hashes,
                            panels, len, W, reinterpret_cast<const unsigned long long *>(table), slots - 1,
                            phash, pport, reinterpret_cast<unsigned long long *>(first));
@@ -3847,9 +3479,11 @@ int csa_legacy_find(csa_instance *I, int32_t k, uint64_t seed, uint64_t panel_be
         return rc;
     if (attempts_out && (rc = dalloc(&attempts.p, n_panels))) return rc;
     HIPCHK(hipMemset(status.p, 0, 16));
-    if ((rc = launch_draw(I, k, seed, panel_begin, n_panels, max_attempts, 0, 0, panels.p, nullptr, attempts.p,
-                          picks.p, status.p, nullptr, nullptr, nullptr, nullptr)))
-        return rc;
+    DrawRequest rq;  // (on the null stream)
+    rq.a.k = k, rq.a.seed = seed, rq.a.panel_begin = panel_begin, rq.a.n_panels = n_panels;
+    rq.a.max_attempts = max_attempts;
+    rq.a.panels = panels.p, rq.a.attempts = attempts.p, rq.a.picks = picks.p, rq.a.status = status.p;
+    if ((rc = launch_draw(I, rq))) return rc;
     uint32_t hs[4];
     if ((rc = read_status(status.p, nullptr, hs))) return rc;
     if ((rc = csa_status_decode(hs))) return rc;
@@ -3872,9 +3506,12 @@ int csa_legacy_attempt(csa_instance *I, int32_t k, uint64_t seed, uint64_t panel
         return rc;
     HIPCHK(hipMemset(status.p, 0, 16));
     HIPCHK(hipMemset(picks.p, 0xFF, std::max(k, 1) * 4));
-    if ((rc = launch_draw(I, k, seed, panel, 1, 1, attempt, 1, panels.p, nullptr, nullptr, picks.p, status.p, sel.p,
-                          rem.p, present.p, nullptr)))
-        return rc;
+    DrawRequest rq;  // one attempt of one panel, on the null stream
+    rq.a.k = k, rq.a.seed = seed, rq.a.panel_begin = panel, rq.a.n_panels = 1;
+    rq.a.max_attempts = 1, rq.a.attempt_base = attempt, rq.a.single = 1;
+    rq.a.panels = panels.p, rq.a.picks = picks.p, rq.a.status = status.p;
+    rq.a.sel_out = sel.p, rq.a.rem_out = rem.p, rq.a.present_out = present.p;
+    if ((rc = launch_draw(I, rq))) return rc;
     uint32_t hs[4];
     if ((rc = read_status(status.p, nullptr, hs))) return rc;
     if (hs[0] == CSA_E_NO_CANDIDATE) return csa_status_decode(hs);

@@ -263,7 +263,8 @@ int csa_draw_kernel_name(const csa_instance *inst, int32_t k, char *buf, uint64_
 
 /* Names of every draw-kernel instantiation the dispatcher can resolve (batch draws and the GENERAL
  * kernels of csa_legacy_find / single attempts / index-list re-draws), newline-separated, spelled as
- * csa_draw_kernel_name spells them and taken from the dispatch tables themselves.  Needs no device.
+ * csa_draw_kernel_name spells them: one line per row of the table of built kernels the dispatcher
+ * looks its kernel up in (kDrawKernels, csrc/draw_dispatch.inc), in no particular order.  Needs no device.
  * CSA_E_INVALID when buf is NULL or len is too small; csa_last_error then names the size needed. */
 int csa_draw_kernel_list(char *buf, uint64_t len);
 

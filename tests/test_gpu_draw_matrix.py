@@ -1,6 +1,7 @@
 """Every draw-kernel instantiation the library can launch, each against the C oracle.
 
-``csa_draw_kernel_list`` names what the dispatcher (pick_draw_config) can resolve; CELLS holds one
+``csa_draw_kernel_list`` names what the dispatcher (pick_draw_config) can resolve: the rows of the table
+of built kernels it looks its kernel up in (kDrawKernels, csrc/draw_dispatch.inc).  CELLS holds one
 synthetic instance per name, the smallest that routes there, and test_matrix_covers_every_built_kernel
 (no GPU) fails when the two sets differ.  Each cell then checks, bit for bit against
 ``oracle.coracle.draw`` on the same instance:
