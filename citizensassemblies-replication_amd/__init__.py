@@ -26,6 +26,12 @@ results and a WeightedCompositionHistogram (per group, the summed probability of
 for bit what group_whist_host adds on the host); composition_difference sets two compositions against
 each other (LEGACY against LEXIMIN)
 
+plus the run as a distribution over whole panels: legacy_panel_distribution(instance, iterations, seed)
+returns legacy_probabilities' results and a PanelDistribution (how often each distinct panel was drawn,
+from uq_mult_kernel / unique_mult_kernel and mult_spectrum_kernel on the device: the multiplicity
+spectrum, sample coverage, the Chao1 bound on the panels possible, the most frequent panels);
+panel_multiplicities_host is the same list in numpy
+
 plus xmin._get_panel_not_in_portfolio_if_possible (XMIN's LEGACY caller,
 xmin.py:464-474) on the device.
 """
@@ -33,12 +39,13 @@ from .instance import Instance, read_instance, encode  # noqa: F401
 from .legacy import SelectionError, check_min_cats, find_random_sample_legacy, seed, set_rng_mode  # noqa: F401
 from .analysis import PairHistogram, PanelSet, legacy_find, legacy_find_batch, legacy_probabilities  # noqa: F401
 from .analysis import leximin_probabilities, portfolio_probabilities, xmin_probabilities  # noqa: F401
-from .analysis import legacy_composition  # noqa: F401
+from .analysis import legacy_composition, legacy_panel_distribution  # noqa: F401
 from .analysis import leximin_composition, portfolio_composition, xmin_composition  # noqa: F401
 from .stats import (CompositionHistogram, GroupSet, agent_groups, feature_groups, group_composition,  # noqa: F401
                     intersection_groups, intersectional_representation)
 from .stats import (WeightedCompositionHistogram, composition_difference, group_whist_host,  # noqa: F401
                     portfolio_group_composition)
+from .stats import PanelDistribution, panel_multiplicities_host  # noqa: F401
 from . import _native, xmin  # noqa: F401
 
 __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_cats",
@@ -47,4 +54,5 @@ __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_c
            "portfolio_probabilities", "legacy_composition", "CompositionHistogram", "GroupSet", "agent_groups",
            "feature_groups", "group_composition", "intersection_groups", "intersectional_representation",
            "leximin_composition", "xmin_composition", "portfolio_composition", "WeightedCompositionHistogram",
-           "composition_difference", "group_whist_host", "portfolio_group_composition"]
+           "composition_difference", "group_whist_host", "portfolio_group_composition",
+           "legacy_panel_distribution", "PanelDistribution", "panel_multiplicities_host"]

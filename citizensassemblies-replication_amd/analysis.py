@@ -25,6 +25,9 @@ Kept names and semantics (reference file:line):
     ``xmin_composition``,              composition of the portfolio (stats.WeightedCompositionHistogram) from
     ``portfolio_composition``          whist_count_kernel + whist_sum_kernel over the same upload -- float64
                                        sums in portfolio order, bit for bit stats.group_whist_host's.
+  * ``legacy_panel_distribution``      new: ``legacy_probabilities`` with a fourth result, how often each
+                                       distinct panel was drawn (stats.PanelDistribution) from uq_mult_kernel /
+                                       unique_mult_kernel and mult_spectrum_kernel beside the distinct count.
 The LEXIMIN / XMIN solvers (Gurobi) and the plotting code stay in the reference (CPU).
 """
 import ctypes
@@ -405,10 +408,13 @@ class LegacyRaw:
     """Integer results of one legacy_probabilities run (exact, before division).  ``stats``: the
     run's draw statistics (attempts, SelectionErrors, min-quota rejections; see draw_stats)."""
 
-    def __init__(self, counts, pairs, unique, panels, attempts, stats=None, composition=None):
+    def __init__(self, counts, pairs, unique, panels, attempts, stats=None, composition=None, multiplicity=None):
         self.counts, self.pairs, self.unique, self.panels, self.attempts = counts, pairs, unique, panels, attempts
         self.stats = stats
         self.composition = composition     # host int64[G, k + 1] when the run was given groups
+        # when the run was asked for multiplicities: (first, mult) device lists of `unique` uint32 words,
+        # the host spectrum and the sum of the squared multiplicities
+        self.multiplicity = multiplicity
 
 
 STAT_KEYS = ("attempts", "selection_errors", "rejections")
@@ -492,7 +498,7 @@ def cached_pipeline(enc, k, chunk):
 
 
 def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20, host_panels=None,
-                         host_stats=None, groups=None):
+                         host_stats=None, groups=None, multiplicity=False):
     """One legacy_probabilities batch on the device through a DevicePipeline cached with the
     encoding (picks / XT / scratch buffers reused across calls).  Panels and hashes of the whole
     batch go to fresh device tensors (the exact distinct count needs all of them; with
@@ -503,7 +509,11 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
     (``host_stats``: that draw's statistics).  ``groups`` (a stats.GroupSet): group_hist_kernel also
     runs over the batch's panels, after the draws, on the stream of the distinct count -- beside the
     counting and pairs with device draws -- and its int64[G, k + 1] table comes back in the same host
-    copy (``LegacyRaw.composition``); its status lands in the same status block."""
+    copy (``LegacyRaw.composition``); its status lands in the same status block.  ``multiplicity``:
+    csa_unique_mult_async and csa_mult_spectrum_async (4096 bins) follow the distinct count on its stream;
+    the list's length, the spectrum and the summary words ride in the same host copy, the (first,
+    multiplicity) lists stay on the device (``LegacyRaw.multiplicity``).  Only a spectrum that overflows
+    the 4096 bins costs a second pass and copy."""
     import torch
     from .distributed import HashTable
     S = int(S)
@@ -590,6 +600,9 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
                     from .stats import group_hist_device
                     d_hist = torch.zeros(max(n_hist, 1), dtype=torch.int64, device=dev)
                     group_hist_device(panels, S, W, d_masks, len(groups), int(k) + 1, d_hist, pipe.status, ust)
+                if multiplicity:
+                    from .stats import unique_mult_device
+                    m_first, m_mult, m_out = unique_mult_device(hashes, panels, S, W, pipe.status, ust, MULT_BINS)
             if ust is not pipe.stream:
                 pipe.stream.wait_stream(ust)
             # counts, distinct count, draw statistics and status in ONE copy: the call's one host wait
@@ -599,6 +612,10 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
                 N.check(N.lib().csa_instance_draw_stats_async(enc.handle, N.ptr(st_d),
                                                               ctypes.c_void_p(pipe.stream.cuda_stream)))
                 parts.append(st_d)
+            n_mult = 0
+            if multiplicity:
+                n_mult = m_out.numel()
+                parts.append(m_out)
             if groups is not None:
                 parts.append(d_hist[:n_hist])
             h = torch.cat(parts + [pipe.status.to(torch.int64)]).cpu().numpy()
@@ -614,10 +631,41 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
             stats = dict(zip(STAT_KEYS, (int(x) for x in h[n_ + 1:n_ + 4]))) if host_panels is None else host_stats
             comp = h[len(h) - 4 - n_hist:len(h) - 4].reshape(len(groups), int(k) + 1).copy() if groups is not None \
                 else None
+            mult = None
+            if multiplicity:
+                m = h[len(h) - 4 - n_hist - n_mult:len(h) - 4 - n_hist]
+                mult = _multiplicity(m, m_first, m_mult, S, unique, pipe.stream)
         finally:
             pipe.panels, pipe.hashes, pipe.pairs = own_p, own_h, own_pairs
     return LegacyRaw(counts, pairs.view(enc.n, enc.n), unique, panels[: S * W] if keep_panels else None, None,
-                     stats, comp)
+                     stats, comp, mult)
+
+
+MULT_BINS = 4096   # spectrum bins of a multiplicity run's first pass; a longer tail takes a second one
+
+
+def _multiplicity(m, d_first, d_mult, S, unique, stream):
+    """LegacyRaw.multiplicity from the host copy m = [list length, spectrum[MULT_BINS], overflow, max,
+    sum m^2, sum m] and the device lists.  The list must be as long as the distinct count and its
+    multiplicities must sum to S; a spectrum beyond MULT_BINS is taken again with max + 1 bins."""
+    import torch
+    distinct, (over, top, sq, total) = int(m[0]), (int(x) for x in m[1 + MULT_BINS:])
+    if distinct != unique or total != S:
+        raise RuntimeError("panel multiplicities: %d list entries summing to %d, the run counted %d distinct panels "
+                           "in %d draws" % (distinct, total, unique, S))
+    spectrum = m[1:1 + MULT_BINS]
+    if over:
+        with torch.cuda.stream(stream):
+            out = torch.empty(1 + top + 1 + 4, dtype=torch.int64, device=d_mult.device)
+            out[:1] = distinct
+            N.check(N.lib().csa_mult_spectrum_async(N.ptr(d_mult), N.ptr(out), S, N.ptr(out[1:]), top + 1,
+                                                    N.ptr(out[top + 2:]), ctypes.c_void_p(stream.cuda_stream)))
+            t = out.cpu().numpy()
+        if t[top + 2] or int(t[top + 5]) != S:
+            raise RuntimeError("panel multiplicities: the spectrum's second pass disagrees with its first")
+        spectrum = t[1:top + 2]
+    return {"first": d_first[:distinct], "mult": d_mult[:distinct], "spectrum": spectrum[:top + 1].copy(),
+            "sum_squares": sq}
 
 
 def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
@@ -645,9 +693,10 @@ def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
     return _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, None)[:3]
 
 
-def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, groups):
+def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, groups, multiplicity=False):
     """legacy_probabilities' body; with ``groups`` (a stats.GroupSet) the run also counts the panels'
-    composition.  Returns (alloc, found_panels, pair_histogram, CompositionHistogram or None)."""
+    composition.  Returns (alloc, found_panels, pair_histogram, CompositionHistogram or None), and with
+    ``multiplicity`` (one process, no ``devices``) a fifth entry, the run's stats.PanelDistribution."""
     from . import distributed as D
     mode = rng or _legacy.RNG_MODE
     if mode not in ("philox", "mt"):
@@ -662,8 +711,10 @@ def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, gr
         st = np.zeros(3, np.uint64)
         picks, panels, _ = mt_draw(enc, instance.k, S, stats=st)
         raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, host_panels=panels,
-                                   host_stats=dict(zip(STAT_KEYS, (int(x) for x in st))), groups=groups)
-        return finish(instance, enc, raw, S) + (composition(groups, raw, S, instance.k),)
+                                   host_stats=dict(zip(STAT_KEYS, (int(x) for x in st))), groups=groups,
+                                   multiplicity=multiplicity)
+        return finish(instance, enc, raw, S) + (composition(groups, raw, S, instance.k),) + \
+            panel_distribution(enc, raw, S)
     if D.world_size() > 1:
         out = D.legacy_probabilities_distributed(instance, iterations, random_seed, keep_panels=keep_panels,
                                                  groups=groups)
@@ -675,8 +726,9 @@ def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, gr
         raw = legacy_sample_raw(enc, instance.k, S, random_seed, want_pairs=True, want_panels=keep_panels,
                                 devices=devices)
         return finish(instance, enc, raw, S) + (None,)
-    raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, groups=groups)
-    return finish(instance, enc, raw, S) + (composition(groups, raw, S, instance.k),)
+    raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, groups=groups,
+                               multiplicity=multiplicity)
+    return finish(instance, enc, raw, S) + (composition(groups, raw, S, instance.k),) + panel_distribution(enc, raw, S)
 
 
 def composition(groups, raw, S, k):
@@ -685,6 +737,41 @@ def composition(groups, raw, S, k):
         return None
     from .stats import CompositionHistogram
     return CompositionHistogram(groups.labels, raw.composition, S, k)
+
+
+def panel_distribution(enc, raw, S):
+    """(stats.PanelDistribution,) of a run that was asked for multiplicities, () without."""
+    m = raw.multiplicity
+    if m is None:
+        return ()
+    from .stats import PanelDistribution
+    return (PanelDistribution(S, m["first"], m["mult"], raw.panels, enc.n, enc.agent_ids, spectrum=m["spectrum"],
+                              sum_squares=m["sum_squares"]),)
+
+
+def legacy_panel_distribution(instance: Instance, iterations: int, random_seed: int, *, rng: str = None,
+                              keep_panels: bool = True):
+    """``legacy_probabilities`` plus the run as a distribution over whole panels: returns
+    ``(alloc, found_panels, pair_histogram, panel_distribution)``.
+
+    The first three are what ``legacy_probabilities(instance, iterations, random_seed, rng=rng,
+    keep_panels=keep_panels)`` returns, bit for bit.  ``panel_distribution`` is a
+    ``stats.PanelDistribution``: how often each distinct panel was drawn (uq_mult_kernel /
+    unique_mult_kernel over the hashes and panels the distinct count already holds, on its side
+    stream), the multiplicity spectrum (mult_spectrum_kernel; it rides in the call's one host copy),
+    and from them the sample coverage, the Chao1 bound on the panels possible, the collision
+    probability and the most frequent panels.  The list stays on the device until read.  The list's
+    length must equal ``len(found_panels)`` and the multiplicities must sum to ``iterations``:
+    RuntimeError otherwise.  ``rng="mt"`` runs the same passes over the host-drawn panels.  With
+    ``keep_panels=False`` the spectrum and estimators work; ``top`` / ``count`` raise.  Sharded runs
+    are not offered: with torch.distributed initialised and world size > 1 the call raises
+    NotImplementedError (the counts would have to travel with the exchange's 24-byte keys)."""
+    from . import distributed as D
+    if D.world_size() > 1:
+        raise NotImplementedError("legacy_panel_distribution: sharded runs (world size %d) are not supported"
+                                  % D.world_size())
+    out = _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, None, multiplicity=True)
+    return out[:3] + (out[4],)
 
 
 def legacy_composition(instance: Instance, iterations: int, random_seed: int, groups, *, rng: str = None,

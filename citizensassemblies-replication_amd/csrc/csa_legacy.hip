@@ -18,7 +18,8 @@
 // and, for the LEXIMIN / XMIN analysis side (analysis.py:194-228), portfolio_pairs_kernel
 // (portfolio.inc): float64 sums of panel probabilities per pair and person, in portfolio order, and
 // whist_count_kernel + whist_sum_kernel (portfolio_composition.inc): the same ordered sums per group
-// and number of members held.
+// and number of members held; and, beside the distinct count, uq_mult_kernel / unique_mult_kernel +
+// mult_emit_kernel / mult_spectrum_kernel (multiplicity.inc): how often each distinct panel was drawn.
 // The C ABI is declared in include/csa_legacy.h.
 #include <hip/hip_runtime.h>
 
@@ -1751,6 +1752,7 @@ __global__ __launch_bounds__(256) void pair_histogram_lds_kernel(const int64_t *
 #include "portfolio.inc"
 #include "composition.inc"
 #include "portfolio_composition.inc"
+#include "multiplicity.inc"
 
 }  // namespace
 
@@ -2062,11 +2064,10 @@ void uq_plan(uint64_t n, UqPlan &q) {
     q.fits = n < (1ull << 31) && n / q.P <= 2048;
 }
 
-int uq_partitioned(const uint64_t *d_hashes, const uint64_t *d_panels, uint64_t n, int W, const UqPlan &q,
-                   uint32_t *scratch, uint64_t *d_unique, uint32_t *d_status, uint32_t seg_cap,
-                   const uint64_t *seg_counts, uint32_t *rep, unsigned long long *rep_count, hipStream_t st) {
-    if (!q.fits) return fail(CSA_E_UNSUPPORTED, "distinct panels: %llu entries exceed the partitioned path",
-                             (unsigned long long)n);
+// the four partitioning passes over scratch = idx[n] | hist[P nwg] | tot[P] | base[P + 1]: idx holds the
+// entry indices grouped by partition, the returned base[] the partitions' bounds in it
+uint32_t *uq_partition(const uint64_t *d_hashes, uint64_t n, const UqPlan &q, uint32_t *scratch, uint32_t seg_cap,
+                       const uint64_t *seg_counts, hipStream_t st) {
     uint32_t *idx = scratch, *hist = idx + n, *tot = hist + q.P * q.nwg, *pbase = tot + q.P;
     hipLaunchKernelGGL(uq_count_kernel, dim3(q.nwg), dim3(kUqThreads), 0, st, d_hashes, n, q.CH, q.pbits, q.nwg, hist,
                        seg_cap, seg_counts);
@@ -2074,6 +2075,15 @@ int uq_partitioned(const uint64_t *d_hashes, const uint64_t *d_panels, uint64_t 
     hipLaunchKernelGGL(uq_scan_tot_kernel, dim3(1), dim3(1024), 0, st, tot, (uint32_t)q.P, pbase);
     hipLaunchKernelGGL(uq_scatter_kernel, dim3(q.nwg), dim3(kUqThreads), 0, st, d_hashes, n, q.CH, q.pbits, q.nwg,
                        hist, pbase, idx, seg_cap, seg_counts);
+    return pbase;
+}
+
+int uq_partitioned(const uint64_t *d_hashes, const uint64_t *d_panels, uint64_t n, int W, const UqPlan &q,
+                   uint32_t *scratch, uint64_t *d_unique, uint32_t *d_status, uint32_t seg_cap,
+                   const uint64_t *seg_counts, uint32_t *rep, unsigned long long *rep_count, hipStream_t st) {
+    if (!q.fits) return fail(CSA_E_UNSUPPORTED, "distinct panels: %llu entries exceed the partitioned path",
+                             (unsigned long long)n);
+    uint32_t *idx = scratch, *pbase = uq_partition(d_hashes, n, q, scratch, seg_cap, seg_counts, st);
     hipLaunchKernelGGL(uq_dedupe_kernel, dim3((unsigned)q.P), dim3(kUqThreads), 0, st, d_hashes, d_panels, W, idx,
                        pbase, reinterpret_cast<unsigned long long *>(d_unique), d_status, rep, rep_count);
     HIPCHK(hipGetLastError());
@@ -2932,6 +2942,70 @@ int csa_unique_segments_async(const uint64_t *d_hashes, const uint64_t *d_panels
         return fail(CSA_E_INVALID, "unique segments: bad arguments");
     return unique_impl(d_hashes, d_panels, (uint64_t)n_segments * capacity, W, d_table, table_slots, d_unique,
                        d_status, (uint32_t)capacity, d_seg_counts, (hipStream_t)stream);
+}
+
+// Panel multiplicities (multiplicity.inc).  Scratch: the partitioned pass's layout, or the global
+// table's u64[slots] followed by its u32[slots] counters (slots = pow2 >= 2n, >= 64); the larger covers both.
+static uint64_t mult_global_slots(uint64_t n) { return pow2_at_least(std::max<uint64_t>(2 * n, 64)); }
+
+uint64_t csa_unique_mult_scratch_bytes(uint64_t n_panels) {
+    const uint64_t n = std::max<uint64_t>(n_panels, 1);
+    UqPlan q;
+    uq_plan(n, q);
+    return std::max<uint64_t>(q.scratch_bytes, 12 * mult_global_slots(n));
+}
+
+int csa_unique_mult_async(const uint64_t *d_hashes, const uint64_t *d_panels, uint64_t n_panels, int32_t W,
+                          void *d_scratch, uint64_t scratch_bytes, uint32_t *d_first, uint32_t *d_mult,
+                          uint64_t *d_distinct, uint32_t *d_status, void *stream) {
+    if (W < 1 || !d_distinct) return fail(CSA_E_INVALID, "unique mult: bad arguments");
+    if (n_panels && (!d_hashes || !d_panels || !d_scratch || !d_first || !d_mult))
+        return fail(CSA_E_INVALID, "unique mult: NULL pointer with %llu panels", (unsigned long long)n_panels);
+    if (n_panels >= (1ull << 32)) return fail(CSA_E_UNSUPPORTED, "unique mult: n_panels >= 2^32 (u32 indices)");
+    if (n_panels && scratch_bytes < csa_unique_mult_scratch_bytes(n_panels))
+        return fail(CSA_E_INVALID, "unique mult: scratch_bytes < csa_unique_mult_scratch_bytes(n_panels)");
+    const hipStream_t st = (hipStream_t)stream;
+    unsigned long long *len = reinterpret_cast<unsigned long long *>(d_distinct);
+    HIPCHK(hipMemsetAsync(len, 0, 8, st));
+    if (n_panels == 0) return CSA_OK;
+    UqPlan q;
+    uq_plan(n_panels, q);
+    const char *ue = getenv("CSA_UNIQUE_PART");
+    if (d_status && n_panels >= 65536 && q.fits && q.scratch_bytes <= scratch_bytes && !(ue && atoi(ue) == 0)) {
+        uint32_t *idx = static_cast<uint32_t *>(d_scratch);
+        uint32_t *pbase = uq_partition(d_hashes, n_panels, q, idx, 0, nullptr, st);
+        hipLaunchKernelGGL(uq_mult_kernel, dim3((unsigned)q.P), dim3(kUqThreads), 0, st, d_hashes, d_panels, W, idx,
+                           pbase, d_status, d_first, d_mult, len);
+        HIPCHK(hipGetLastError());
+        return CSA_OK;
+    }
+    const uint64_t slots = mult_global_slots(n_panels);
+    unsigned long long *table = static_cast<unsigned long long *>(d_scratch);
+    uint32_t *ctr = reinterpret_cast<uint32_t *>(table + slots);
+    HIPCHK(hipMemsetAsync(table, 0, slots * 12, st));
+    hipLaunchKernelGGL(unique_mult_kernel, dim3((unsigned)((n_panels + 255) / 256)), dim3(256), 0, st, d_hashes, d_panels,
+                       n_panels, W, table, slots - 1, ctr);
+    hipLaunchKernelGGL(mult_emit_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, table, ctr, slots,
+                       d_first, d_mult, len);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+int csa_mult_spectrum_async(const uint32_t *d_mult, const uint64_t *d_distinct, uint64_t capacity,
+                            uint64_t *d_spectrum, uint64_t n_bins, uint64_t *d_summary, void *stream) {
+    if (n_bins < 1 || !d_spectrum || !d_summary || !d_distinct || (capacity && !d_mult))
+        return fail(CSA_E_INVALID, "mult spectrum: bad arguments");
+    const hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(d_spectrum, 0, n_bins * 8, st));
+    HIPCHK(hipMemsetAsync(d_summary, 0, 32, st));
+    if (capacity == 0) return CSA_OK;
+    const unsigned grid = (unsigned)std::min<uint64_t>((capacity + kMsThreads - 1) / kMsThreads, kMsMaxBlocks);
+    hipLaunchKernelGGL(mult_spectrum_kernel, dim3(grid), dim3(kMsThreads), 0, st, d_mult,
+                       reinterpret_cast<const unsigned long long *>(d_distinct), capacity,
+                       reinterpret_cast<unsigned long long *>(d_spectrum), n_bins, n_bins <= (uint64_t)kMsLdsBins ? 1 : 0,
+                       reinterpret_cast<unsigned long long *>(d_summary));
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
 }
 
 // scratch of csa_exchange_pack_async: rep_count, rep[n], then the partitioned pass's scratch or --

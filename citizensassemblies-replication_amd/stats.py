@@ -532,6 +532,232 @@ def portfolio_group_composition(groups, panels, weights, k, stream=None):
     return WeightedCompositionHistogram(groups.labels, h[:G * bins].reshape(G, bins).copy(), total, P, k)
 
 
+# ---- panel multiplicities: the run as a distribution over whole panels -----------------------------
+#
+# LEXIMIN's portfolio is a distribution over panels; a LEGACY run of S draws is a sample of one.  The
+# distinct count alone (found_panels) is a sample-size-limited number; how often each distinct panel was
+# drawn gives the multiplicity spectrum, the sample coverage, a lower bound on the panels possible and
+# the most likely panels.  On the device the list comes from csa_unique_mult_async (the dedupe's own
+# table slots, csrc/multiplicity.inc); ``panel_multiplicities_host`` is the same contract in numpy.
+
+def panel_multiplicities_host(panels):
+    """(first int64[u], mult int64[u]) of packed panels uint64[S, W], ascending in ``first``: per distinct
+    row the lowest index at which it occurs and the number of rows equal to it."""
+    p = np.ascontiguousarray(panels, np.uint64)
+    if p.ndim != 2:
+        raise ValueError("panels must be uint64[S, W]")
+    if len(p) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    _, first, mult = np.unique(p, axis=0, return_index=True, return_counts=True)
+    order = np.argsort(first, kind="stable")
+    return first[order].astype(np.int64), mult[order].astype(np.int64)
+
+
+def _pack_ids(panel, agent_ids, W):
+    """One agent-id tuple -> uint64[W] row in encoding order; KeyError for an id that is no agent."""
+    pos = {aid: q for q, aid in enumerate(agent_ids)}
+    row = np.zeros(max(W, 1), np.uint64)
+    for aid in panel:
+        q = pos[aid]
+        row[q >> 6] |= np.uint64(1) << np.uint64(q & 63)
+    return row
+
+
+class PanelDistribution:
+    """How often each distinct panel of a run of ``S`` draws occurred.
+
+    ``distinct`` = number of distinct panels D, ``spectrum`` (host int64, length ``max_multiplicity``
+    + 1) with ``spectrum[j]`` = f_j, the panels seen exactly j times (``spectrum[0]`` is 0),
+    ``sum_squares`` = the sum of the squared multiplicities.
+
+    ``first`` / ``mult`` list, per distinct panel, its lowest draw index and its count, in any order:
+    host arrays, or device tensors (as csa_unique_mult_async leaves them), which stay on the device
+    until read.  ``panels``: the run's S packed panels (host uint64[S, W], or the device tensor of S*W
+    words) from which ``top`` / ``count`` read the rows at the first indices; None when the panels
+    were not kept -- then the spectrum and the estimators work and ``top`` / ``count`` raise
+    RuntimeError.  Pickles hold host arrays only (the list, and the D distinct rows when panels were
+    kept), so they load where no GPU is visible.
+
+    Degenerate runs: S = 0 has no panels, spectrum [0], and coverage, chao1, collision_probability and
+    max_probability all 0.0.  S = 1 has coverage 0.0, chao1 1.0 and collision_probability 0.0 (no pair
+    of draws exists).  With f_1 = 0 (every panel seen at least twice) coverage is 1.0 and chao1 is D.
+    """
+
+    _where = "panels were not kept; only len() is available"  # analysis.PanelSet's message
+
+    def __init__(self, S, first, mult, panels=None, n=0, agent_ids=None, spectrum=None, sum_squares=None):
+        self.S = int(S)
+        self._n, self._ids = int(n), agent_ids
+        self._W = max((self._n + 63) // 64, 1)
+        self._first, self._mult = first, mult      # any order; sorted by first index when first read
+        self._sorted = False
+        self._panels = panels                      # all S rows (indexed by first), or with _rows: the D rows
+        self._rows = False
+        self.distinct = int(len(first))
+        if spectrum is None or sum_squares is None:
+            m = self._host(mult)
+            spectrum = np.bincount(m, minlength=1) if len(m) else np.zeros(1, np.int64)
+            sum_squares = sum(int(x) * int(x) for x in m.tolist())
+        self.spectrum = np.ascontiguousarray(spectrum, np.int64)
+        self.sum_squares = int(sum_squares)
+        self.max_multiplicity = len(self.spectrum) - 1
+        j = np.arange(len(self.spectrum), dtype=np.int64)
+        if int(self.spectrum.sum()) != self.distinct or int((self.spectrum * j).sum()) != self.S:
+            raise ValueError("multiplicities of %d panels summing to %d do not describe %d draws of %d distinct panels"
+                             % (int(self.spectrum.sum()), int((self.spectrum * j).sum()), self.S, self.distinct))
+
+    @staticmethod
+    def _host(a):
+        if _is_device_tensor(a):
+            return a.cpu().numpy().astype(np.int64) & 0xFFFFFFFF     # the device lists are uint32 words
+        return np.asarray(a, np.int64)
+
+    def __len__(self):
+        return self.distinct
+
+    def _f(self, j):
+        return int(self.spectrum[j]) if j < len(self.spectrum) else 0
+
+    def coverage(self):
+        """Good-Turing sample coverage 1 - f_1 / S: the probability mass of the panels seen."""
+        return 1 - self._f(1) / self.S if self.S else 0.0
+
+    def chao1(self):
+        """Chao1 lower bound on the number of possible panels, D + f_1 (f_1 - 1) / (2 (f_2 + 1))."""
+        f1, f2 = self._f(1), self._f(2)
+        return self.distinct + f1 * (f1 - 1) / (2 * (f2 + 1))
+
+    def collision_probability(self):
+        """The unbiased estimate of the sum of squared panel probabilities (LEXIMIN's concentration
+        measure): (sum m^2 - S) / (S (S - 1)), the share of pairs of draws that gave the same panel."""
+        S = self.S
+        return (self.sum_squares - S) / (S * (S - 1)) if S > 1 else 0.0
+
+    def max_probability(self):
+        """The most frequent panel's share of the draws."""
+        return self.max_multiplicity / self.S if self.S else 0.0
+
+    def _sort(self):
+        """The list ascending in first index (on the device while it is there)."""
+        if not self._sorted:
+            if _is_device_tensor(self._first):
+                import torch
+                f = self._first.to(torch.int64) & 0xFFFFFFFF
+                f, order = torch.sort(f)
+                self._first, self._mult = f, (self._mult.to(torch.int64) & 0xFFFFFFFF)[order]
+            else:
+                f, m = np.asarray(self._first, np.int64), np.asarray(self._mult, np.int64)
+                order = np.argsort(f, kind="stable")
+                self._first, self._mult = f[order], m[order]
+                if self._rows:
+                    self._panels = self._panels[order]
+            self._sorted = True
+        return self._first, self._mult
+
+    def multiplicities(self):
+        """Host ``(first int64[D], mult int64[D])`` ascending in first index."""
+        f, m = self._sort()
+        if _is_device_tensor(f):
+            f, m = f.cpu().numpy(), m.cpu().numpy()
+        return f.copy(), m.copy()
+
+    def _panel_rows(self, where):
+        """uint64[len(where), W]: the panels of the sorted list's entries ``where``."""
+        if self._panels is None:
+            raise RuntimeError(self._where)
+        f, _ = self._sort()
+        W = self._W
+        if self._rows:
+            return self._panels[np.asarray(where, np.int64)]
+        if _is_device_tensor(self._panels):
+            import torch
+            at = f[torch.as_tensor(where, dtype=torch.int64, device=f.device)] if _is_device_tensor(f) else \
+                torch.as_tensor(np.asarray(f)[np.asarray(where, np.int64)], device=self._panels.device)
+            rows = self._panels[:self.S * W].view(self.S, W)[at.to(self._panels.device)]
+            return np.ascontiguousarray(rows.cpu().numpy()).view(np.uint64).reshape(-1, W)
+        fh = f.cpu().numpy() if _is_device_tensor(f) else f
+        p = np.ascontiguousarray(self._panels).view(np.uint64).reshape(-1, W)
+        return p[fh[np.asarray(where, np.int64)]]
+
+    def _decode(self, row):
+        from .instance import unpack_panel
+        return tuple(self._ids[q] for q in unpack_panel(row, self._n))
+
+    def top(self, m):
+        """The ``m`` most frequent panels as ``[(sorted agent-id tuple, count), ...]``, most frequent
+        first, ties in the order of their first draw.  A device list is sorted on the device and only
+        the m rows are copied."""
+        if self._panels is None:
+            raise RuntimeError(self._where)
+        f, mult = self._sort()
+        m = max(0, min(int(m), self.distinct))
+        if _is_device_tensor(mult):
+            import torch
+            cnt, where = torch.sort(mult, descending=True, stable=True)   # stable: first index breaks ties
+            cnt, where = cnt[:m].cpu().numpy(), where[:m].cpu().numpy()
+        else:
+            where = np.argsort(-mult, kind="stable")[:m]
+            cnt = mult[where]
+        rows = self._panel_rows(where)
+        return [(self._decode(r), int(c)) for r, c in zip(rows, cnt)]
+
+    def count(self, panel):
+        """How often ``panel`` (agent ids, any order) was drawn; 0 for a panel never drawn."""
+        if self._panels is None:
+            raise RuntimeError(self._where)
+        row = _pack_ids(panel, self._ids, self._W)
+        f, mult = self._sort()
+        if _is_device_tensor(self._panels) and not self._rows:
+            import torch
+            dev = self._panels.device
+            at = f if _is_device_tensor(f) else torch.as_tensor(f, device=dev)
+            rows = self._panels[:self.S * self._W].view(self.S, self._W)[at]
+            hit = (rows == torch.from_numpy(row.view(np.int64)).to(dev)).all(dim=1).nonzero().reshape(-1).cpu().numpy()
+        else:
+            hit = np.flatnonzero((self._panel_rows(np.arange(self.distinct)) == row).all(axis=1))
+        if len(hit) == 0:
+            return 0
+        return int(mult[int(hit[0])].item()) if _is_device_tensor(mult) else int(mult[hit[0]])
+
+    def __getstate__(self):
+        f, m = self.multiplicities()
+        rows = self._panel_rows(np.arange(self.distinct)) if self._panels is not None else None
+        return {"S": self.S, "n": self._n, "ids": self._ids, "first": f, "mult": m, "rows": rows,
+                "spectrum": self.spectrum, "sum_squares": self.sum_squares}
+
+    def __setstate__(self, st):
+        self.S, self._n, self._ids = st["S"], st["n"], st["ids"]
+        self._W = max((self._n + 63) // 64, 1)
+        self._first, self._mult, self._sorted = st["first"], st["mult"], True
+        self._panels, self._rows = st["rows"], st["rows"] is not None
+        self.distinct = len(self._first)
+        self.spectrum, self.sum_squares = st["spectrum"], st["sum_squares"]
+        self.max_multiplicity = len(self.spectrum) - 1
+
+
+def unique_mult_device(d_hashes, d_panels, S, W, d_status, stream, n_bins=4096):
+    """Enqueue csa_unique_mult_async + csa_mult_spectrum_async over a batch's device hashes and panels on
+    ``stream`` (a torch stream); nothing waits.  Returns (first, mult, out): two int32 tensors of
+    max(S, 1) uint32 words, and int64 ``out`` = [list length, spectrum[n_bins], overflow, max,
+    sum m^2, sum m].  The scratch is allocated here on that stream and goes back to torch's allocator,
+    which reuses it only for work ordered after this on the same stream."""
+    import torch
+    L = N.lib()
+    S, W, n_bins = int(S), int(W), int(n_bins)
+    dev = d_hashes.device
+    with torch.cuda.stream(stream):
+        need = int(L.csa_unique_mult_scratch_bytes(S))
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        first = torch.empty(max(S, 1), dtype=torch.int32, device=dev)
+        mult = torch.empty(max(S, 1), dtype=torch.int32, device=dev)
+        out = torch.empty(1 + n_bins + 4, dtype=torch.int64, device=dev)
+    sp = ctypes.c_void_p(stream.cuda_stream)
+    N.check(L.csa_unique_mult_async(N.ptr(d_hashes), N.ptr(d_panels), S, W, N.ptr(scratch), need, N.ptr(first),
+                                    N.ptr(mult), N.ptr(out), N.ptr(d_status), sp))
+    N.check(L.csa_mult_spectrum_async(N.ptr(mult), N.ptr(out), S, N.ptr(out[1:]), n_bins, N.ptr(out[1 + n_bins:]), sp))
+    return first, mult, out
+
+
 def composition_difference(a, b):
     """Two compositions over equal labels and k (CompositionHistogram or WeightedCompositionHistogram,
     either side: LEGACY against LEXIMIN, LEXIMIN against XMIN) compared group by group.  Returns a dict of

@@ -347,6 +347,41 @@ int csa_unique_segments_async(const uint64_t *d_hashes, const uint64_t *d_panels
                               uint64_t capacity, const uint64_t *d_seg_counts, int32_t W, uint64_t *d_table,
                               uint64_t table_slots, uint64_t *d_unique, uint32_t *d_status, void *stream);
 
+/* Panel multiplicities: the batch as a distribution over whole panels.  For every distinct panel of
+ * d_hashes / d_panels (n_panels entries; the equality rule is csa_unique_async's: equal 128-bit hashes
+ * AND equal W-word bitmasks) one list entry: d_first[e] = the LOWEST index at which the panel occurs,
+ * d_mult[e] = the number of entries that hold it.  d_first / d_mult: n_panels uint32 each; *d_distinct
+ * (uint64) is WRITTEN with the list's length (not accumulated).  The order of the list is
+ * unspecified and may differ between calls; the set of (first, multiplicity) pairs is exact and
+ * deterministic, and the multiplicities sum to n_panels.
+ * d_scratch: csa_unique_mult_scratch_bytes(n_panels) bytes (covers both paths below; monotone in
+ * n_panels).  Paths as csa_unique_async, the scratch taking the table's place: with d_status, from
+ * 65536 entries on and unless CSA_UNIQUE_PART=0, the partitioned pass (per-partition LDS tables);
+ * otherwise -- or with d_status == NULL -- one global table.  A partition with more than 8192
+ * distinct panels sets CSA_E_UNSUPPORTED in d_status exactly as csa_unique_async does; the list of
+ * such a call is not to be used (it is never silently short: the status says so).
+ * Stream-ordered, no host wait, nothing allocated.  n_panels == 0 writes *d_distinct = 0 and launches
+ * nothing else.  n_panels < 2^32 (CSA_E_UNSUPPORTED above).  CSA_E_INVALID, before any device call,
+ * for W < 1, a NULL d_distinct, any other NULL pointer (d_status aside) with n_panels > 0, or
+ * scratch_bytes below csa_unique_mult_scratch_bytes(n_panels). */
+uint64_t csa_unique_mult_scratch_bytes(uint64_t n_panels);
+int csa_unique_mult_async(const uint64_t *d_hashes, const uint64_t *d_panels, uint64_t n_panels, int32_t W,
+                          void *d_scratch, uint64_t scratch_bytes, uint32_t *d_first, uint32_t *d_mult,
+                          uint64_t *d_distinct, uint32_t *d_status, void *stream);
+
+/* Multiplicity spectrum of a list csa_unique_mult_async wrote: d_spectrum[m] (n_bins uint64, zeroed
+ * by the call) = number of list entries with multiplicity m < n_bins, over the first
+ * min(*d_distinct, capacity) entries of d_mult -- the length is read on the device, entries past it
+ * are never read.  d_summary (4 uint64, zeroed by the call): [0] entries with multiplicity >= n_bins
+ * (not in the spectrum), [1] the largest multiplicity, [2] the sum of the squared multiplicities,
+ * [3] the sum of the multiplicities -- which equals the number of entries the list was made from and
+ * is the pass's self-check.  With n_bins = [1] + 1 nothing overflows.  Every n_bins >= 1 is served
+ * (a per-workgroup LDS histogram up to 8192 bins, straight to d_spectrum above).  Stream-ordered, no
+ * host wait.  CSA_E_INVALID, before any device call, for n_bins < 1 or a NULL pointer (d_mult may be
+ * NULL with capacity == 0). */
+int csa_mult_spectrum_async(const uint32_t *d_mult, const uint64_t *d_distinct, uint64_t capacity,
+                            uint64_t *d_spectrum, uint64_t n_bins, uint64_t *d_summary, void *stream);
+
 /* Multi-GPU distinct-panel exchange, send side (no host synchronisation; replaces the reference's
  * per-run `found_panels` set, analysis.py:171,186, across ranks).  The exact LOCAL distinct panels
  * of d_hashes / d_panels (n_panels, hash AND bitmask equality) are bucketed by owner rank
