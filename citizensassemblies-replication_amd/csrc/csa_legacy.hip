@@ -79,7 +79,27 @@ __device__ __forceinline__ void philox4x32_10(uint32_t &c0, uint32_t &c1, uint32
     }
 }
 
+// select_bit's last two levels as a table held in two literals: byte m (0..7) is the entry of the nibbles
+// m and m + 8, with the position of the r-th set bit of m in bits 2r, 2r + 1 (r = 1..3).  A rank past
+// m's own bits can only mean the nibble's bit 3, so those fields, and bits 0-1, hold 3: bit 3 of the
+// nibble never has to be looked at.  (tests/test_select_bit_host.py rebuilds the literals.)
+constexpr uint32_t sel_nibble_entry(int m) {
+    uint32_t e = 3u;
+    int r = 1;
+    for (int b = 0; b < 3; ++b)
+        if (m >> b & 1) e |= (uint32_t)b << (2 * r++);
+    for (; r <= 3; ++r) e |= 3u << (2 * r);
+    return e;
+}
+constexpr uint32_t sel_nibble_word(int m0) {
+    return sel_nibble_entry(m0) | sel_nibble_entry(m0 + 1) << 8 | sel_nibble_entry(m0 + 2) << 16 | sel_nibble_entry(m0 + 3) << 24;
+}
+constexpr uint32_t kSelNibbleLo = 0xD3F7F3FFu, kSelNibbleHi = 0x93E7E3FBu;  // entries 0-3, 4-7
+static_assert(kSelNibbleLo == sel_nibble_word(0) && kSelNibbleHi == sel_nibble_word(4), "select_bit's nibble table");
+
 // position (0..63) of the rr-th (1-based) set bit of m; requires 1 <= rr <= popcount(m)
+// (TABLE = false: the search goes down to single bits, for the one kernel the table's register costs a wave)
+template <bool TABLE = true>
 __device__ __forceinline__ int select_bit(uint64_t m, int rr) {
     // the 32-bit half first, then a binary search on 32-bit values (no 64-bit masks or shifts)
     uint32_t x = (uint32_t)m;
@@ -91,7 +111,7 @@ __device__ __forceinline__ int select_bit(uint64_t m, int rr) {
         pos = 32;
     }
 #pragma unroll
-    for (int s = 16; s >= 1; s >>= 1) {
+    for (int s = 16; s >= (TABLE ? 4 : 1); s >>= 1) {
         const int c = __popc(x & ((1u << s) - 1u));
         if (rr > c) {
             rr -= c;
@@ -99,7 +119,11 @@ __device__ __forceinline__ int select_bit(uint64_t m, int rr) {
             pos += s;
         }
     }
-    return pos;
+    if constexpr (!TABLE) return pos;
+    // the nibble x & 15 and a rank 1..4 are left: the position comes from kSelNibble, one v_perm_b32 with
+    // the nibble's low three bits as the selector (its other selector bytes are 0: result bytes 1-3 are
+    // entry 0 = 0xFF) and one bit-field extract at 2 rr; rank 4 reads the two bits above the entry, 3
+    return pos + (int)((__builtin_amdgcn_perm(kSelNibbleHi, kSelNibbleLo, x & 7u) >> (2 * rr)) & 3u);
 }
 
 __device__ __forceinline__ uint64_t fmix_a(uint64_t z) {  // splitmix64 finaliser

@@ -188,7 +188,8 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                 // is slower, not wrong).
                 // kPredicated: <16, 28, 5, true> is the one FN = 16 form that fits 4 waves per SIMD
                 // (128 VGPRs; the launch bounds ask for 3) and either predicated block costs it that
-                // wave (139 / 129 VGPRs), so it keeps the selects and the v_bitop3 drop.
+                // wave (139 / 129 VGPRs), so it keeps the selects and the v_bitop3 drop -- and select_bit's
+                // search down to single bits, whose nibble table costs it the same wave.
                 constexpr bool kPredicated = !(FN == 16 && WN == 28 && NP == 5 && K8);
                 int acc = 0, base = 0, wsp = 0;
                 uint64_t ma = 0ull, mb = 0ull;
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(kSoloThreads, FN <= 8 ? CSA_SOLO_OCC8 : CSA_SOLO_OC
                 const bool second = r - base > c0;  // the holder is in the pair's second word
                 const uint64_t ms = second ? mb : ma;
                 const int ws = wsp + (int)second;
-                const int b = select_bit(ms, r - base - (second ? c0 : 0));
+                const int b = select_bit<kPredicated>(ms, r - base - (second ? c0 : 0));  // (129 VGPRs with the nibble table)
                 const int p = ws * 64 + b;
                 const uint32_t hb = pm[p];
                 // drop the pick from the register pool while the pm[p] read is in flight (none of it
