@@ -164,6 +164,19 @@ def check(rc):
     return rc
 
 
+def raise_status(words):
+    """Raise the error of a device status block (its four 32-bit words on the host): KeyError("") for a missing
+    candidate, as legacy.py:188, CsaError (csa_status_decode names the panel) otherwise.  Returns on a clean block."""
+    import numpy as np
+    h = np.ascontiguousarray(words, np.uint32)
+    if not h[0]:
+        return
+    rc = lib().csa_status_decode(ptr(h))
+    if rc == CSA_E_NO_CANDIDATE:
+        raise KeyError("")
+    check(rc)
+
+
 def draw_kernel_list():
     """Names of every draw-kernel instantiation the library can launch (csa_draw_kernel_list; no device)."""
     buf = ctypes.create_string_buffer(1 << 14)

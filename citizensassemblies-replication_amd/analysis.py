@@ -32,6 +32,7 @@ The LEXIMIN / XMIN solvers (Gurobi) and the plotting code stay in the reference 
 """
 import ctypes
 import os
+from collections import namedtuple
 from typing import Dict, List, Tuple
 
 import numpy as np
@@ -497,6 +498,34 @@ def cached_pipeline(enc, k, chunk):
     return pipe
 
 
+def read_draw_stats(enc, out, stream):
+    """The instance's draw statistics into ``out`` (three int64 device words), ordered on ``stream``: no host wait."""
+    N.check(N.lib().csa_instance_draw_stats_async(enc.handle, N.ptr(out), ctypes.c_void_p(stream.cuda_stream)))
+
+
+def distinct_table(enc, S, dev):
+    """The encoding's cached distinct-count table (distributed.HashTable), grown to hold S panels.  A batch takes it
+    BEFORE its draws: allocated on the pipeline stream, which the draw stream waits on, and the side stream on that."""
+    table = getattr(enc, "_table", None)
+    if table is None or table.device != dev:
+        from .distributed import HashTable
+        table = enc._table = HashTable(S, dev)
+    table.ensure(S)
+    return table
+
+
+def enqueue_group_hist(groups, d_masks, panels, S, W, k, status, stream):
+    """group_hist_kernel over a batch's S device panels on ``stream``, into a zeroed int64[G, k + 1] table (made on
+    that stream; at least one element, so G = 0 still has something to reduce and copy).  Returns the flat table;
+    errors land in ``status``.  ``d_masks``: ``groups.device_masks(device, W)``."""
+    import torch
+    from .stats import group_hist_device
+    with torch.cuda.stream(stream):
+        d_hist = torch.zeros(max(len(groups) * (k + 1), 1), dtype=torch.int64, device=panels.device)
+    group_hist_device(panels, S, W, d_masks, len(groups), k + 1, d_hist, status, stream)
+    return d_hist
+
+
 def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20, host_panels=None,
                          host_stats=None, groups=None, multiplicity=False):
     """One legacy_probabilities batch on the device through a DevicePipeline cached with the
@@ -515,8 +544,7 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
     multiplicity) lists stay on the device (``LegacyRaw.multiplicity``).  Only a spectrum that overflows
     the 4096 bins costs a second pass and copy."""
     import torch
-    from .distributed import HashTable
-    S = int(S)
+    S, k = int(S), int(k)
     C = max(1, min(S, int(chunk)))
     pipe = cached_pipeline(enc, k, C)
     W = enc.W
@@ -532,30 +560,17 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
         pipe.reset(pairs=False, counts=host_panels is not None, status=not one)
         if host_panels is None and not one:
             reset_draw_stats(enc, pipe.stream)
-        own_p, own_h, own_pairs = pipe.panels, pipe.hashes, pipe.pairs
-        pipe.pairs = pairs
-        # the distinct-count table (zero-filled on allocation, on this stream) before the draws: the
-        # draw stream waits on this stream, and the distinct count's side stream on the draw stream
-        table = getattr(enc, "_table", None)
-        if table is None or table.device != dev:
-            table = enc._table = HashTable(S, dev)
-        table.ensure(S)
-        n_hist = 0
-        if groups is not None:
-            if groups.W != W:
-                raise ValueError("groups of another encoding: W = %d, the instance has %d" % (groups.W, W))
-            n_hist = len(groups) * (int(k) + 1)
-            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
-        try:
-            drawn = None  # what the distinct count's side stream waits for: the draws
+        table = distinct_table(enc, S, dev)
+        d_masks = groups.device_masks(dev, W) if groups is not None else None
+        drawn = None  # what the distinct count's side stream waits for: the draws
+        with pipe.bound(panels=pipe.panels, hashes=pipe.hashes, pairs=pairs):
             if one:
                 # one chunk: draw on the pipeline stream; draw_lane_kernel's fused pack also writes the XT
                 # blocks (csa_draw_xt_async), so the counting is the pair kernel alone and the counts
                 # are the pair diagonal -- the transpose pass leaves the call's serial tail
                 pipe.panels, pipe.hashes = panels[:S * W], hashes[:2 * S]
                 xt_done = pipe.draw_xt(random_seed, 0, S, reset=True)
-                drawn = torch.cuda.Event()
-                drawn.record(pipe.stream)
+                drawn = pipe.stream.record_event()
                 if not xt_done:
                     pipe.counts.zero_()
                     pipe.transpose_count(S)
@@ -567,6 +582,7 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
                 # (DevicePipeline.draw_count_chunks); two draw streams were measured slower
                 # (profiles/r04f_draw_streams/)
                 pipe.draw_count_chunks(random_seed, 0, S, panels, hashes, C, overwrite_pairs=True, reset_counts=True)
+                drawn = pipe.draw_stream.record_event()
             else:
                 for off in range(0, S, C):
                     ln = min(C, S - off)
@@ -576,94 +592,62 @@ def legacy_sample_device(enc, k, S, random_seed, keep_panels=True, chunk=1 << 20
                     pipe.hash(ln)
                     pipe.transpose_count(ln)
                     pipe.pair_counts(ln, overwrite=off == 0)
-            if S == 0:
-                pairs.zero_()
-            # the distinct count needs only the draws (hashes, panels): with device draws it runs on a
-            # side stream beside the counting and pairs of the last chunk, and the pipeline stream
-            # waits for it before the one host read.  Everything it touches is ordered on that stream:
-            # the counter reset, the table, and the hand-back (pipeline stream waits on the side stream)
-            ust = pipe.stream
-            if host_panels is None:
-                ust = getattr(pipe, "unique_stream", None)
-                if ust is None:
-                    ust = pipe.unique_stream = torch.cuda.Stream(dev)
-                if drawn is not None:
-                    ust.wait_event(drawn)
-                else:
-                    ust.wait_stream(pipe.draw_stream)  # (the draw stream itself waited on the pipeline stream)
-            with torch.cuda.stream(ust):
-                table.count.zero_()
-                N.check(N.lib().csa_unique_async(N.ptr(hashes), N.ptr(panels), S, W, N.ptr(table.table), table.slots,
-                                                 N.ptr(table.count), N.ptr(pipe.status),
-                                                 ctypes.c_void_p(ust.cuda_stream)))
-                if groups is not None:
-                    from .stats import group_hist_device
-                    d_hist = torch.zeros(max(n_hist, 1), dtype=torch.int64, device=dev)
-                    group_hist_device(panels, S, W, d_masks, len(groups), int(k) + 1, d_hist, pipe.status, ust)
-                if multiplicity:
-                    from .stats import unique_mult_device
-                    m_first, m_mult, m_out = unique_mult_device(hashes, panels, S, W, pipe.status, ust, MULT_BINS)
-            if ust is not pipe.stream:
-                pipe.stream.wait_stream(ust)
-            # counts, distinct count, draw statistics and status in ONE copy: the call's one host wait
-            parts = [pipe.counts, table.count]
-            if host_panels is None:
-                st_d = torch.zeros(3, dtype=torch.int64, device=dev)
-                N.check(N.lib().csa_instance_draw_stats_async(enc.handle, N.ptr(st_d),
-                                                              ctypes.c_void_p(pipe.stream.cuda_stream)))
-                parts.append(st_d)
-            n_mult = 0
-            if multiplicity:
-                n_mult = m_out.numel()
-                parts.append(m_out)
-            if groups is not None:
-                parts.append(d_hist[:n_hist])
-            h = torch.cat(parts + [pipe.status.to(torch.int64)]).cpu().numpy()
-            n_ = enc.n
-            status = (h[-4:] & 0xFFFFFFFF).astype(np.uint32)
-            if status[0]:
-                rc = N.lib().csa_status_decode(N.ptr(status))
-                if rc == N.CSA_E_NO_CANDIDATE:
-                    raise KeyError("")       # legacy.py:188
-                N.check(rc)
-            counts = h[:n_].copy()
-            unique = int(h[n_])
-            stats = dict(zip(STAT_KEYS, (int(x) for x in h[n_ + 1:n_ + 4]))) if host_panels is None else host_stats
-            comp = h[len(h) - 4 - n_hist:len(h) - 4].reshape(len(groups), int(k) + 1).copy() if groups is not None \
-                else None
-            mult = None
-            if multiplicity:
-                m = h[len(h) - 4 - n_hist - n_mult:len(h) - 4 - n_hist]
-                mult = _multiplicity(m, m_first, m_mult, S, unique, pipe.stream)
-        finally:
-            pipe.panels, pipe.hashes, pipe.pairs = own_p, own_h, own_pairs
+        if S == 0:
+            pairs.zero_()
+        # the group histogram and the multiplicity passes ride on the distinct count's stream, before its hand-back
+        ust = pipe.distinct_count(table, hashes, panels, S, drawn)
+        if groups is not None:
+            d_hist = enqueue_group_hist(groups, d_masks, panels, S, W, k, pipe.status, ust)
+        if multiplicity:
+            from .stats import unique_mult_device
+            m_first, m_mult, m_out = unique_mult_device(hashes, panels, S, W, pipe.status, ust, MULT_BINS)
+        pipe.rejoin(ust)
+        # counts, distinct count, draw statistics and status in ONE copy: the call's one host wait
+        fields = [("counts", pipe.counts), ("unique", table.count)]
+        if host_panels is None:
+            st_d = torch.zeros(3, dtype=torch.int64, device=dev)
+            read_draw_stats(enc, st_d, pipe.stream)
+            fields.append(("stats", st_d))
+        if multiplicity:
+            fields += zip(MULT_FIELDS, m_out.split([1, MULT_BINS, 4]))
+        if groups is not None:
+            fields.append(("hist", d_hist))
+        h, status = pipe.host_fields(fields)
+        N.raise_status(status)
+        counts = h["counts"].copy()
+        unique = int(h["unique"][0])
+        stats = dict(zip(STAT_KEYS, (int(x) for x in h["stats"]))) if host_panels is None else host_stats
+        comp = h["hist"][:len(groups) * (k + 1)].reshape(len(groups), k + 1).copy() if groups is not None else None
+        mult = _multiplicity(h, m_first, m_mult, S, unique, pipe.stream) if multiplicity else None
     return LegacyRaw(counts, pairs.view(enc.n, enc.n), unique, panels[: S * W] if keep_panels else None, None,
                      stats, comp, mult)
 
 
 MULT_BINS = 4096   # spectrum bins of a multiplicity run's first pass; a longer tail takes a second one
+# stats.unique_mult_device's output record: [list length | spectrum[bins] | overflow, max, sum m^2, sum m]
+MULT_FIELDS = ("mult_length", "mult_spectrum", "mult_sums")
 
 
-def _multiplicity(m, d_first, d_mult, S, unique, stream):
-    """LegacyRaw.multiplicity from the host copy m = [list length, spectrum[MULT_BINS], overflow, max,
-    sum m^2, sum m] and the device lists.  The list must be as long as the distinct count and its
-    multiplicities must sum to S; a spectrum beyond MULT_BINS is taken again with max + 1 bins."""
+def _multiplicity(h, d_first, d_mult, S, unique, stream):
+    """LegacyRaw.multiplicity from the host copy ``h`` of unique_mult_device's record (MULT_FIELDS) and the
+    device lists.  The list must be as long as the distinct count and its multiplicities must sum to S; a
+    spectrum beyond MULT_BINS is taken again with max + 1 bins."""
     import torch
-    distinct, (over, top, sq, total) = int(m[0]), (int(x) for x in m[1 + MULT_BINS:])
+    length, spectrum, sums = (h[f] for f in MULT_FIELDS)
+    distinct, (over, top, sq, total) = int(length[0]), (int(x) for x in sums)
     if distinct != unique or total != S:
         raise RuntimeError("panel multiplicities: %d list entries summing to %d, the run counted %d distinct panels "
                            "in %d draws" % (distinct, total, unique, S))
-    spectrum = m[1:1 + MULT_BINS]
     if over:
         with torch.cuda.stream(stream):
             out = torch.empty(1 + top + 1 + 4, dtype=torch.int64, device=d_mult.device)
-            out[:1] = distinct
-            N.check(N.lib().csa_mult_spectrum_async(N.ptr(d_mult), N.ptr(out), S, N.ptr(out[1:]), top + 1,
-                                                    N.ptr(out[top + 2:]), ctypes.c_void_p(stream.cuda_stream)))
-            t = out.cpu().numpy()
-        if t[top + 2] or int(t[top + 5]) != S:
+            d_len, d_spectrum, d_sums = out.split([1, top + 1, 4])
+            d_len[:] = distinct
+            N.check(N.lib().csa_mult_spectrum_async(N.ptr(d_mult), N.ptr(out), S, N.ptr(d_spectrum), top + 1,
+                                                    N.ptr(d_sums), ctypes.c_void_p(stream.cuda_stream)))
+            _, spectrum, again = (t.numpy() for t in out.cpu().split([1, top + 1, 4]))
+        if again[0] or int(again[3]) != S:
             raise RuntimeError("panel multiplicities: the spectrum's second pass disagrees with its first")
-        spectrum = t[1:top + 2]
     return {"first": d_first[:distinct], "mult": d_mult[:distinct], "spectrum": spectrum[:top + 1].copy(),
             "sum_squares": sq}
 
@@ -693,10 +677,15 @@ def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
     return _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, None)[:3]
 
 
+# what one LEGACY run gives, the public calls take their slice: composition (a stats.CompositionHistogram) for a
+# run given groups, distribution (a stats.PanelDistribution) for one asked for multiplicities, None otherwise
+LegacyRun = namedtuple("LegacyRun", "alloc panels histogram composition distribution", defaults=(None, None))
+
+
 def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, groups, multiplicity=False):
-    """legacy_probabilities' body; with ``groups`` (a stats.GroupSet) the run also counts the panels'
-    composition.  Returns (alloc, found_panels, pair_histogram, CompositionHistogram or None), and with
-    ``multiplicity`` (one process, no ``devices``) a fifth entry, the run's stats.PanelDistribution."""
+    """legacy_probabilities' body, returning a LegacyRun; with ``groups`` (a stats.GroupSet) the run also
+    counts the panels' composition, with ``multiplicity`` (one process, no ``devices``) how often each
+    distinct panel was drawn."""
     from . import distributed as D
     mode = rng or _legacy.RNG_MODE
     if mode not in ("philox", "mt"):
@@ -713,22 +702,25 @@ def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, gr
         raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, host_panels=panels,
                                    host_stats=dict(zip(STAT_KEYS, (int(x) for x in st))), groups=groups,
                                    multiplicity=multiplicity)
-        return finish(instance, enc, raw, S) + (composition(groups, raw, S, instance.k),) + \
-            panel_distribution(enc, raw, S)
-    if D.world_size() > 1:
-        out = D.legacy_probabilities_distributed(instance, iterations, random_seed, keep_panels=keep_panels,
-                                                 groups=groups)
-        return out if groups is not None else out + (None,)
-    seed(random_seed)
-    enc.check_quotas(instance.k)
-    STREAM.take_panels(S)
-    if devices is not None:
-        raw = legacy_sample_raw(enc, instance.k, S, random_seed, want_pairs=True, want_panels=keep_panels,
-                                devices=devices)
-        return finish(instance, enc, raw, S) + (None,)
-    raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, groups=groups,
-                               multiplicity=multiplicity)
-    return finish(instance, enc, raw, S) + (composition(groups, raw, S, instance.k),) + panel_distribution(enc, raw, S)
+    elif D.world_size() > 1:
+        return LegacyRun(*D.legacy_probabilities_distributed(instance, iterations, random_seed,
+                                                             keep_panels=keep_panels, groups=groups))
+    else:
+        seed(random_seed)
+        enc.check_quotas(instance.k)
+        STREAM.take_panels(S)
+        if devices is not None:
+            raw = legacy_sample_raw(enc, instance.k, S, random_seed, want_pairs=True, want_panels=keep_panels,
+                                    devices=devices)
+        else:
+            raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, groups=groups,
+                                       multiplicity=multiplicity)
+    m, dist = raw.multiplicity, None
+    if m is not None:
+        from .stats import PanelDistribution
+        dist = PanelDistribution(S, m["first"], m["mult"], raw.panels, enc.n, enc.agent_ids, spectrum=m["spectrum"],
+                                 sum_squares=m["sum_squares"])
+    return LegacyRun(*finish(instance, enc, raw, S), composition(groups, raw, S, instance.k), dist)
 
 
 def composition(groups, raw, S, k):
@@ -737,16 +729,6 @@ def composition(groups, raw, S, k):
         return None
     from .stats import CompositionHistogram
     return CompositionHistogram(groups.labels, raw.composition, S, k)
-
-
-def panel_distribution(enc, raw, S):
-    """(stats.PanelDistribution,) of a run that was asked for multiplicities, () without."""
-    m = raw.multiplicity
-    if m is None:
-        return ()
-    from .stats import PanelDistribution
-    return (PanelDistribution(S, m["first"], m["mult"], raw.panels, enc.n, enc.agent_ids, spectrum=m["spectrum"],
-                              sum_squares=m["sum_squares"]),)
 
 
 def legacy_panel_distribution(instance: Instance, iterations: int, random_seed: int, *, rng: str = None,
@@ -770,8 +752,8 @@ def legacy_panel_distribution(instance: Instance, iterations: int, random_seed: 
     if D.world_size() > 1:
         raise NotImplementedError("legacy_panel_distribution: sharded runs (world size %d) are not supported"
                                   % D.world_size())
-    out = _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, None, multiplicity=True)
-    return out[:3] + (out[4],)
+    run = _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, None, multiplicity=True)
+    return run.alloc, run.panels, run.histogram, run.distribution
 
 
 def legacy_composition(instance: Instance, iterations: int, random_seed: int, groups, *, rng: str = None,
@@ -788,10 +770,8 @@ def legacy_composition(instance: Instance, iterations: int, random_seed: int, gr
     ``rng="mt"`` runs the same pass over the host-drawn panels.  With torch.distributed initialised
     and world size > 1 the call is sharded like ``legacy_probabilities`` and every rank returns the
     whole job's table (summed over the ranks)."""
-    from .stats import GroupSet
-    if not isinstance(groups, GroupSet):
-        raise TypeError("groups must be a stats.GroupSet")
-    return _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, groups)
+    _check_groups(instance, groups)
+    return _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, groups)[:4]
 
 
 def finish(instance, enc, raw, S):
@@ -890,6 +870,7 @@ def _portfolio_run(instance, portfolio, probabilities, min_probability, groups):
     in the same host copy as ``alloc``.  Returns (alloc, panels, pair_histogram,
     WeightedCompositionHistogram or None)."""
     import torch
+    from .device import StatusBlock
     enc = encode_cached(instance.categories, instance.agents)
     ids, n = enc.agent_ids, enc.n
     pos = getattr(enc, "_pos", None)
@@ -902,33 +883,28 @@ def _portfolio_run(instance, portfolio, probabilities, min_probability, groups):
     G, bins = (len(groups), int(instance.k) + 1) if groups is not None else (0, 0)
     tri = torch.empty(max(m, 1), dtype=torch.float64, device="cuda")
     # alloc, then the composition table and its status words: one tensor, one host copy
-    out = torch.empty(max(n, 1) + (G * bins + 2 if groups is not None else 0), dtype=torch.float64, device="cuda")
-    d_alloc = out[:max(n, 1)]
-    d_rows, d_w = _portfolio_launch(rows, weights, n, tri, d_alloc)
+    out = StatusBlock([("alloc", max(n, 1))] + ([("table", max(G * bins, 1))] if groups is not None else []),
+                      torch.float64, "cuda", status=groups is not None)
+    d_rows, d_w = _portfolio_launch(rows, weights, n, tri, out.views["alloc"])
     if groups is not None:
         from . import stats as St
-        dev = out.device
+        dev = out.out.device
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev)
-            table, status = out[max(n, 1):max(n, 1) + G * bins], out[max(n, 1) + G * bins:].view(torch.int32)
-            status.zero_()
-            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
-            St.group_whist_device(d_rows, len(weights) if n else 0, enc.W, d_w, d_masks, G, bins, table, status, st)
+            St.group_whist_device(d_rows, len(weights) if n else 0, enc.W, d_w, groups.device_masks(dev), G, bins,
+                                  out.views["table"], out.status, torch.cuda.current_stream(dev))
     # the panel set while the device works: members in ascending position (np.nonzero walks row-major)
     names = list(map(ids.__getitem__, np.nonzero(x)[1].tolist()))
     ends = np.cumsum(np.count_nonzero(x, axis=1)).tolist()
     panels = {tuple(names[a:b]) for a, b, (_, pob) in zip([0] + ends[:-1], ends, pairs)
               if min_probability is None or pob > min_probability}
     total = St.portfolio_total(weights) if groups is not None else None
-    h = out.cpu().numpy()                                                # the call's one host wait
-    alloc = dict(zip(ids, h[:n].tolist()))
+    h, words = out.host()                                                # the call's one host wait
+    alloc = dict(zip(ids, h["alloc"][:n].tolist()))
     comp = None
     if groups is not None:
-        words = h[max(n, 1) + G * bins:].view(np.uint32)
-        if words[0]:
-            N.check(N.lib().csa_status_decode(N.ptr(np.ascontiguousarray(words))))
-        comp = St.WeightedCompositionHistogram(groups.labels, h[max(n, 1):max(n, 1) + G * bins].reshape(G, bins).copy(),
-                                               total, len(weights), instance.k)
+        N.raise_status(words)
+        comp = St.WeightedCompositionHistogram(groups.labels, h["table"][:G * bins].reshape(G, bins).copy(), total,
+                                               len(weights), instance.k)
     return alloc, panels, PairHistogram._from_device_triangle(n, tri), comp
 
 
@@ -938,9 +914,7 @@ def _check_groups(instance, groups):
     from .stats import GroupSet
     if not isinstance(groups, GroupSet):
         raise TypeError("groups must be a stats.GroupSet")
-    W = max((len(instance.agents) + 63) // 64, 1)
-    if groups.W != W:
-        raise ValueError("groups of another encoding: W = %d, the instance has %d" % (groups.W, W))
+    groups.check_width(max((len(instance.agents) + 63) // 64, 1))
 
 
 def portfolio_composition(instance: Instance, portfolio, probabilities, groups, min_probability=None):

@@ -18,7 +18,10 @@ Buffers are allocated once for the largest shard and reused across runs, so a
 timed loop measures kernels only.
 """
 import ctypes
+import functools
+import os
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -26,6 +29,50 @@ from . import _native as N
 
 def _stream_ptr(stream):
     return ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+
+
+@functools.lru_cache(maxsize=None)
+def _record(layout, dtype):
+    """The layout of a host copy, ((name, length), ...) of ``dtype`` elements one after the other, as a numpy
+    record type: a copy viewed through it is read by name, and numpy keeps the offsets."""
+    return np.dtype([(name, dtype, (ln,)) for name, ln in layout])
+
+
+class _Bound:
+    """DevicePipeline.bound's ``with`` object: a plain save and restore of the pipeline's attributes."""
+    __slots__ = ("pipe", "buffers", "own")
+
+    def __init__(self, pipe, buffers):
+        self.pipe, self.buffers = pipe, buffers
+
+    def __enter__(self):
+        attrs = vars(self.pipe)
+        self.own = {name: attrs[name] for name in self.buffers}
+        attrs.update(self.buffers)
+        return self.pipe
+
+    def __exit__(self, *exc):
+        vars(self.pipe).update(self.own)
+
+
+class StatusBlock:
+    """One device tensor of 64-bit elements that kernels write into directly: named fields, then
+    (``status=True``) a status block, its four int32 words viewed over the last two elements and zeroed
+    here.  ``views[name]`` / ``status`` are the device views; ``host()`` is the one copy, read back by
+    the same names."""
+
+    def __init__(self, fields, dtype, device, status=True, zero=False):
+        self.layout = tuple((name, int(ln)) for name, ln in fields) + ((("status", 2),) if status else ())
+        sizes = [ln for _, ln in self.layout]
+        self.out = (torch.zeros if zero else torch.empty)(sum(sizes), dtype=dtype, device=device)
+        self.views = dict(zip((name for name, _ in self.layout), self.out.split(sizes)))
+        self.status = self.views.pop("status").view(torch.int32).zero_() if status else None
+
+    def host(self):
+        """(host, status as uint32[4] or None) from one copy, the caller's host wait; ``host[name]``: that field."""
+        copy = self.out.cpu().numpy()
+        host = copy.view(_record(self.layout, copy.dtype))[0]
+        return host, (host["status"].view(np.uint32) if self.status is not None else None)
 
 
 def chunk_plan(S, C, R):
@@ -105,6 +152,51 @@ class DevicePipeline:
                 self.unique.zero_()
             if pairs and self.pairs is not None:
                 self.pairs.zero_()
+
+    BUFFERS = frozenset(("panels", "hashes", "xt", "pairs", "counts"))
+
+    def bound(self, **buffers):
+        """Rebind the named buffers (``panels=, hashes=, xt=, pairs=, counts=``) for the stages run
+        inside the ``with`` block -- which may go on assigning them, chunk by chunk -- and put back what
+        they were on exit, also after an exception."""
+        if not buffers.keys() <= self.BUFFERS:
+            raise TypeError("bound: no such buffer: %s" % ", ".join(sorted(buffers.keys() - self.BUFFERS)))
+        return _Bound(self, buffers)
+
+    def distinct_count(self, table, hashes, panels, S, after):
+        """Enqueue the exact distinct count of a batch (csa_unique_async into ``table``, a HashTable) and return
+        the stream it runs on.  It needs only the draws (hashes, panels): with device draws it runs on the
+        pipeline's side stream, which waits for ``after`` -- an event recorded behind the draws (the draw stream
+        itself waited on the pipeline stream) -- and so runs beside the counting and pairs of the last chunk.
+        Everything the count touches is ordered on that stream: the counter reset, the table, and the hand-back
+        (``rejoin``, before the call's one host read); further passes over the same hashes and panels go on it in
+        between.  ``after=None`` (host-drawn panels): the pipeline stream itself."""
+        ust = self.stream
+        if after is not None:
+            ust = getattr(self, "unique_stream", None)
+            if ust is None:
+                ust = self.unique_stream = torch.cuda.Stream(self.device)
+            ust.wait_event(after)
+        with torch.cuda.stream(ust):
+            table.count.zero_()
+            N.check(N.lib().csa_unique_async(N.ptr(hashes), N.ptr(panels), S, self.enc.W, N.ptr(table.table),
+                                             table.slots, N.ptr(table.count), N.ptr(self.status), _stream_ptr(ust)))
+        return ust
+
+    def host_fields(self, fields):
+        """Named 1-D int64 device tensors ((name, tensor), ...; empty ones allowed, none named "status") and the
+        status block (int32[4], widened to int64 for the trip) to the host in ONE concatenation and ONE copy -- a
+        call's one host wait.  Returns (host, status as uint32[4]); ``host[name]`` is that field's int64 array, a
+        view of the copy.  (The layout is worked out after the copy, so only the enqueue stands before the wait.)"""
+        copy = torch.cat([t for _, t in fields] + [self.status.to(torch.int64)]).cpu().numpy()
+        layout = tuple((name, t.numel()) for name, t in fields) + (("status", self.status.numel()),)
+        host = copy.view(_record(layout, copy.dtype))[0]
+        return host, (host["status"] & 0xFFFFFFFF).astype(np.uint32)     # int32 words came sign-extended
+
+    def rejoin(self, ust):
+        """The hand-back of ``distinct_count``: the pipeline stream waits for the side stream's work."""
+        if ust is not self.stream:
+            self.stream.wait_stream(ust)
 
     # individual stages (stream-ordered, no sync) -------------------------------------------
     def draw_picks(self, seed, panel_begin, S, max_attempts=0, stream=None):
@@ -196,7 +288,6 @@ class DevicePipeline:
         (csa_draw_round_panels; 131072 for the two-lane kernel on 256 CUs)."""
         rp = getattr(self, "_round", None)
         if rp is None:
-            import numpy as np
             out = np.zeros(1, np.uint64)
             N.check(N.lib().csa_draw_round_panels(self.enc.handle, self.k, N.ptr(out)))
             rp = self._round = max(1, int(out[0]))
@@ -215,8 +306,6 @@ class DevicePipeline:
         the first chunk's counting), so the draws do not wait for it.  With ``overwrite_pairs`` and
         ``reset_counts`` on an instance whose draw writes XT itself (xt_fused), the chunks take
         _draw_xt_chunks instead: no transpose pass, the counts from the pair diagonal."""
-        import os
-        import torch
         S, C, W = int(S), max(1, min(int(chunk), self.max_panels)), self.enc.W
         # flat cuts by default: the round-aligned plan (CSA_CHUNK_PLAN=round) measured slower end to end
         # (sf_e 10^6 panels 4.59 vs 4.41 ms, example_large_200 1.25e6 5.02 vs 4.99, synthetic8192 10^6
@@ -233,8 +322,7 @@ class DevicePipeline:
         if chunks and self.want_pairs and overwrite_pairs and reset_counts and self.xt_fused() and \
                 os.environ.get("CSA_DRAW_XT", "1") != "0":
             return self._draw_xt_chunks(seed, panel_begin, panels, hashes, chunks, st)
-        own_p, own_h = self.panels, self.hashes
-        try:
+        with self.bound(panels=self.panels, hashes=self.hashes):
             drawn = []
             for off, ln in chunks:
                 self.panels, self.hashes = panels[off * W:(off + ln) * W], hashes[2 * off:2 * (off + ln)]
@@ -253,8 +341,6 @@ class DevicePipeline:
                     # the last chunk's pairs run after every draw of the call: the kernel fastest alone
                     self.pair_counts(ln, overwrite=overwrite_pairs and j == 0, shared=j + 1 < len(chunks),
                                      alone=j + 1 == len(chunks))
-        finally:
-            self.panels, self.hashes = own_p, own_h
 
     def xt_fused(self):
         """True when this instance's batch draw is a register kernel with a fused pack (draw_lane_kernel /
@@ -272,14 +358,12 @@ class DevicePipeline:
         for the pairs of chunk c - XT_RING, which ran long before), and the pipeline stream runs only the
         pair kernel of chunk c after its draw (stored for the first chunk, added after); the counts are the
         pair matrix's diagonal at the end (stored) -- no transpose pass (csa_transpose_count_async)."""
-        import torch
         W = self.enc.W
         ring = getattr(self, "_xt_ring", None)
         if ring is None or ring[0].numel() != self.xt.numel():
             ring = self._xt_ring = [self.xt] + [torch.empty_like(self.xt) for _ in range(self.XT_RING - 1)]
-        own_p, own_h, own_xt = self.panels, self.hashes, self.xt
         drawn, counted, fused = [], [], []
-        try:
+        with self.bound(panels=self.panels, hashes=self.hashes, xt=self.xt):
             def count(j):
                 off, ln = chunks[j]
                 self.stream.wait_event(drawn[j])
@@ -304,8 +388,6 @@ class DevicePipeline:
                     count(j - 1)
             count(len(chunks) - 1)
             self.counts_from_pairs()
-        finally:
-            self.panels, self.hashes, self.xt = own_p, own_h, own_xt
 
     def run(self, seed, panel_begin, S, max_attempts=0, overwrite_pairs=False):
         """Enqueue the whole pass; results accumulate into counts / pairs / unique (pairs are
@@ -320,13 +402,8 @@ class DevicePipeline:
     def check_status(self):
         """Synchronise and raise on a device-side error (no-candidate, attempt limit)."""
         self.stream.synchronize()
-        h = self.status.cpu().numpy().astype("uint32")
-        rc = N.lib().csa_status_decode(N.ptr(h))
-        if rc == N.CSA_E_NO_CANDIDATE:
-            raise KeyError("")       # legacy.py:188
-        N.check(rc)
+        N.raise_status(self.status.cpu().numpy().astype("uint32"))
 
     def panels_view(self, S):
         """Host copy of the packed panels (uint64[S, W])."""
-        import numpy as np
         return self.panels[: S * self.enc.W].cpu().numpy().view(np.uint64).reshape(S, self.enc.W)

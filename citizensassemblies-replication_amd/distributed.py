@@ -373,8 +373,7 @@ def local_distinct_rows(hashes, panels, n, W, status=None, stream=None):
                                             ctypes.c_void_p(st.cuda_stream)))
     st.synchronize()
     if status is None:
-        h = own_status.cpu().numpy().astype(np.uint32)
-        N.check(N.lib().csa_status_decode(N.ptr(h)))
+        N.raise_status(own_status.cpu().numpy().astype(np.uint32))
     cnt = int(send_c.item())
     return send_p[: cnt * W], cnt
 
@@ -421,8 +420,7 @@ def device_redraw(enc, k, seed, device, max_attempts=0):
                                              N.ptr(buf), N.ptr(status), ctypes.c_void_p(st.cuda_stream)))
             host = buf[:count * W].cpu()
             words = status.cpu().numpy().astype(np.uint32)
-        if words[0]:
-            _decode_status(words, int(words[0]))
+        N.raise_status(words)
         return host.numpy().view(np.uint64).reshape(count, W)
 
     return draw
@@ -439,10 +437,7 @@ def _decode_status(words, reduced_code):
     h = np.asarray(words, np.uint32)
     if int(h[0]) != int(reduced_code):
         h = np.array([reduced_code, 0xFFFFFFFF, 0xFFFFFFFF, 0], np.uint32)
-    rc = N.lib().csa_status_decode(N.ptr(h))
-    if rc == N.CSA_E_NO_CANDIDATE:
-        raise KeyError("")
-    N.check(rc)
+    N.raise_status(h)
 
 
 def _shard_exchange(enc, n_max, world, dev):
@@ -506,109 +501,77 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
     local = end - begin
     n_max = shard_range(S, world, 0)[1]          # rank 0 holds the largest share
     dev = shard_device()
-    with torch.cuda.device(dev):
-        out = _sharded_call(A, N, dist, enc, k, S, random_seed, world, begin, local, n_max, dev, keep_panels, chunk,
-                            t0, timings, instance, groups)
-    return out
-
-
-def _sharded_call(A, N, dist, enc, k, S, random_seed, world, begin, local, n_max, dev, keep_panels, chunk, t0, timings,
-                  instance, groups=None):
-    import time
-    import torch
     C = max(1, min(max(local, 1), int(chunk or os.environ.get("CSA_SHARD_CHUNK", 1 << 20))))
-    pipe = A.cached_pipeline(enc, k, C)
-    # (CSA_FORCE_EXCHANGE=1: the key exchange even for one rank -- tests of its collectives on one GPU)
-    ex = _shard_exchange(enc, n_max, world, dev) if world > 1 or os.environ.get("CSA_FORCE_EXCHANGE") == "1" else None
     W, n = enc.W, enc.n
-    L = N.lib()
-    st = pipe.stream
-    sp = ctypes.c_void_p(st.cuda_stream)
-    t1 = time.perf_counter()
-    with torch.cuda.stream(st):
-        panels = torch.empty(max(local * W, 1), dtype=torch.int64, device=dev)
-        hashes = torch.empty(max(2 * local, 2), dtype=torch.int64, device=dev)
-        pairs = torch.empty(n * n, dtype=torch.int64, device=dev)
-        # [counts (n) | attempts, SelectionErrors, rejections | distinct count]: one all_reduce(SUM)
-        acc = torch.zeros(n + 4, dtype=torch.int64, device=dev)
-        pipe.reset(pairs=False)
-        A.reset_draw_stats(enc, st)
-        if ex is None:  # one rank: its distinct-count table before the draws (see below)
-            table = getattr(enc, "_table", None)
-            if table is None or table.device != dev:
-                table = enc._table = HashTable(local, dev)
-            table.ensure(local)
-        own_counts, own_pairs = pipe.counts, pipe.pairs
-        pipe.counts, pipe.pairs = acc[:n], pairs
-        try:
-            if local:
-                pipe.draw_count_chunks(random_seed, begin, local, panels, hashes, C, overwrite_pairs=True,
-                                       reset_counts=True)
-            else:
-                pairs.zero_()
-        finally:
-            pipe.counts, pipe.pairs = own_counts, own_pairs
-        # this shard's draw statistics, before the exchange's re-draws (device, no host wait)
-        N.check(L.csa_instance_draw_stats_async(enc.handle, N.ptr(acc[n:n + 3]), sp))
-        n_hist = 0
-        if groups is not None:
-            # the share's composition table on the pipeline stream (ordered after every draw); with
-            # more than one rank (or a forced exchange) the tables are summed below
-            from .stats import group_hist_device
-            if groups.W != W:
-                raise ValueError("groups of another encoding: W = %d, the instance has %d" % (groups.W, W))
-            n_hist = len(groups) * (k + 1)
-            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
-            d_hist = torch.zeros(max(n_hist, 1), dtype=torch.int64, device=dev)
-            group_hist_device(panels, local, W, d_masks, len(groups), k + 1, d_hist, pipe.status, st)
-        if ex is not None:
-            # a shard whose draw failed still enters the collectives (every rank must, or the others
-            # hang); its status block joins the MAX all_reduce below, so every rank raises the draw's
-            # error -- the exchange writes its own status only past a full segment, and the first
-            # error recorded in a block wins (csa_status_decode)
-            _all_reduce_pairs(pairs, S, st)
-            u = ex.run(hashes, panels, local, status=pipe.status, stream=st, panel_begin=begin,
-                       redraw=(enc.handle, k, random_seed, 0))
-        else:
-            # one rank owns every panel: nothing to reduce, and the exact local distinct count runs on
-            # a side stream after the draws, beside the last chunk's counting and pairs (as
-            # analysis.legacy_sample_device; the table was allocated before the draws were enqueued)
-            ust = getattr(pipe, "unique_stream", None)
-            if ust is None:
-                ust = pipe.unique_stream = torch.cuda.Stream(dev)
-            ust.wait_stream(pipe.draw_stream if local else st)
-            with torch.cuda.stream(ust):
-                table.count.zero_()
-                N.check(L.csa_unique_async(N.ptr(hashes), N.ptr(panels), local, W, N.ptr(table.table),
-                                           table.slots, N.ptr(table.count), N.ptr(pipe.status),
-                                           ctypes.c_void_p(ust.cuda_stream)))
-            st.wait_stream(ust)
-            u = table.count
-        acc[n + 3:].copy_(u)
-        code = pipe.status[:1].to(torch.int64)
-        if ex is not None:
-            _all_reduce(acc)
+    with torch.cuda.device(dev):
+        pipe = A.cached_pipeline(enc, k, C)
+        # (CSA_FORCE_EXCHANGE=1: the key exchange even for one rank -- tests of its collectives on one GPU)
+        ex = _shard_exchange(enc, n_max, world, dev) if world > 1 or os.environ.get("CSA_FORCE_EXCHANGE") == "1" \
+            else None
+        st = pipe.stream
+        t1 = time.perf_counter()
+        with torch.cuda.stream(st):
+            panels = torch.empty(max(local * W, 1), dtype=torch.int64, device=dev)
+            hashes = torch.empty(max(2 * local, 2), dtype=torch.int64, device=dev)
+            pairs = torch.empty(n * n, dtype=torch.int64, device=dev)
+            # [counts (n) | attempts, SelectionErrors, rejections | distinct count]: one all_reduce(SUM)
+            acc = torch.zeros(n + 4, dtype=torch.int64, device=dev)
+            d_counts, d_stats, d_unique = acc.split([n, 3, 1])
+            pipe.reset(pairs=False)
+            A.reset_draw_stats(enc, st)
+            # one rank: its distinct-count table before the draws (analysis.distinct_table)
+            table = A.distinct_table(enc, local, dev) if ex is None else None
+            with pipe.bound(counts=d_counts, pairs=pairs):
+                if local:
+                    pipe.draw_count_chunks(random_seed, begin, local, panels, hashes, C, overwrite_pairs=True,
+                                           reset_counts=True)
+                else:
+                    pairs.zero_()
+            # this shard's draw statistics, before the exchange's re-draws (device, no host wait)
+            A.read_draw_stats(enc, d_stats, st)
+            fields = [("counts", d_counts), ("stats", d_stats), ("unique", d_unique)]
             if groups is not None:
-                _all_reduce(d_hist)
-            # MAX over ranks of a priority key: a draw error (KeyError / attempt limit) on any rank
-            # outranks an exchange error on another (an overflowing segment), whatever their codes
-            code += ERR_DRAW_PRIORITY * ((code == N.CSA_E_NO_CANDIDATE) | (code == N.CSA_E_ATTEMPT_LIMIT))
-            _all_reduce(code, op=dist.ReduceOp.MAX)
-            code %= ERR_DRAW_PRIORITY
-        tail = torch.cat([code, pipe.status.to(torch.int64)])
-        host = torch.cat([acc, tail] + ([d_hist[:n_hist]] if groups is not None else [])).cpu()  # the one host wait
-    t2 = time.perf_counter()
-    h = host.numpy()
-    if int(h[n + 4]):
-        _decode_status((h[n + 5:n + 9] & 0xFFFFFFFF).astype(np.uint32), int(h[n + 4]))
-    counts = h[:n].copy()
-    stats = dict(zip(A.STAT_KEYS, (int(x) for x in h[n:n + 3])))
+                # the share's composition table on the pipeline stream (ordered after every draw); with
+                # more than one rank (or a forced exchange) the tables are summed below
+                d_hist = A.enqueue_group_hist(groups, groups.device_masks(dev, W), panels, local, W, k, pipe.status, st)
+                fields.append(("hist", d_hist))
+            if ex is not None:
+                # a shard whose draw failed still enters the collectives (every rank must, or the others
+                # hang); its status block joins the MAX all_reduce below, so every rank raises the draw's
+                # error -- the exchange writes its own status only past a full segment, and the first
+                # error recorded in a block wins (csa_status_decode)
+                _all_reduce_pairs(pairs, S, st)
+                u = ex.run(hashes, panels, local, status=pipe.status, stream=st, panel_begin=begin,
+                           redraw=(enc.handle, k, random_seed, 0))
+            else:
+                # one rank owns every panel: nothing to reduce, and the exact local distinct count runs on
+                # a side stream after the draws, beside the last chunk's counting and pairs
+                pipe.rejoin(pipe.distinct_count(table, hashes, panels, local,
+                                                (pipe.draw_stream if local else st).record_event()))
+                u = table.count
+            d_unique.copy_(u)
+            code = pipe.status[:1].to(torch.int64)
+            if ex is not None:
+                _all_reduce(acc)
+                if groups is not None:
+                    _all_reduce(d_hist)
+                # MAX over ranks of a priority key: a draw error (KeyError / attempt limit) on any rank
+                # outranks an exchange error on another (an overflowing segment), whatever their codes
+                code += ERR_DRAW_PRIORITY * ((code == N.CSA_E_NO_CANDIDATE) | (code == N.CSA_E_ATTEMPT_LIMIT))
+                _all_reduce(code, op=dist.ReduceOp.MAX)
+                code %= ERR_DRAW_PRIORITY
+            h, words = pipe.host_fields(fields + [("code", code)])     # the one host wait
+        t2 = time.perf_counter()
+    agreed = int(h["code"][0])
+    if agreed:
+        _decode_status(words, agreed)
+    stats = dict(zip(A.STAT_KEYS, (int(x) for x in h["stats"])))
     # one rank (no exchange): its panels are the whole run's, so found_panels keeps them on the device and
     # decodes them when iterated, as the one-GPU call does
     solo = ex is None and keep_panels
-    comp = h[n + 9:n + 9 + n_hist].reshape(len(groups), k + 1).copy() if groups is not None else None
-    raw = A.LegacyRaw(counts, pairs.view(n, n), int(h[n + 3]), panels[: local * W] if solo else None, None, stats,
-                      comp)
+    comp = h["hist"][:len(groups) * (k + 1)].reshape(len(groups), k + 1).copy() if groups is not None else None
+    raw = A.LegacyRaw(h["counts"].copy(), pairs.view(n, n), int(h["unique"][0]), panels[: local * W] if solo else None,
+                      None, stats, comp)
     out = A.finish(instance, enc, raw, S) + ((A.composition(groups, raw, S, k),) if groups is not None else ())
     if keep_panels and not solo:
         # nothing kept, nothing sent: the whole job's panels are re-drawn where they are read

@@ -13,6 +13,7 @@
   there (``torch.sort``) and copied once; other float histograms (uniform, host-built) are
   sorted on the host.
 """
+import contextlib
 import ctypes
 from dataclasses import dataclass
 
@@ -123,6 +124,19 @@ class GroupSet:
 
     def __len__(self):
         return len(self.labels)
+
+    def check_width(self, W):
+        """ValueError unless the masks have the W words of the encoding they are used with."""
+        if self.W != W:
+            raise ValueError("groups of another encoding: W = %d, the instance has %d" % (self.W, W))
+
+    def device_masks(self, device, W=None):
+        """The masks as G*W int64 words on ``device`` (a blocking upload on the current stream), for
+        panels of ``W`` words when given: ValueError for groups of another encoding."""
+        import torch
+        if W is not None:
+            self.check_width(W)
+        return torch.from_numpy(self.masks.view(np.int64).reshape(-1)).to(device)
 
     def __add__(self, other):
         if not isinstance(other, GroupSet):
@@ -258,11 +272,52 @@ def group_hist_host(masks, panels, bins):
     return hist
 
 
-class CompositionHistogram:
+class _Composition:
+    """What both composition tables derive: a subclass names its table (``_table``, [G, k + 1]) and
+    the number it is normalised by (``_norm``), the instance attributes stay its own.  The bin index
+    takes the table's dtype (int64 for counts, float64 for weights), so integer sums stay exact."""
+
+    def __len__(self):
+        return len(self.labels)
+
+    def probabilities(self):
+        """P(a panel holds c members), float64[G, k+1] = table / norm."""
+        return self._table / self._norm
+
+    def mean(self):
+        """Expected members per panel (by linearity also the sum of the members' marginals)."""
+        return (self._table * np.arange(self.k + 1, dtype=self._table.dtype)).sum(axis=1) / self._norm
+
+    def panel_share(self):
+        """mean / k: the panel share plot_intersectional_representation reports."""
+        return self.mean() / self.k
+
+    def variance(self):
+        """Variance of the members per panel (population form: the table is the distribution)."""
+        d = np.arange(self.k + 1, dtype=np.float64)[None, :] - self.mean()[:, None]
+        return (self._table * d * d).sum(axis=1) / self._norm
+
+    def prob_absent(self):
+        """P(a panel holds no member of the group)."""
+        return self._table[:, 0] / self._norm
+
+    def support(self):
+        """(lowest, highest) non-empty bin per group, int64[G] each; (-1, -1) where there is none."""
+        nz = self._table != 0
+        some = nz.any(axis=1)
+        lo = np.where(some, nz.argmax(axis=1), -1)
+        hi = np.where(some, self.k - nz[:, ::-1].argmax(axis=1), -1)
+        return lo.astype(np.int64), hi.astype(np.int64)
+
+
+class CompositionHistogram(_Composition):
     """``counts[g][c]`` = panels of the run holding exactly c members of group g (host int64[G, k+1]),
     over ``S`` panels of size ``k``; ``labels`` name the groups.  Everything derived is float64 from
     the integer counts.  ``a + b`` merges two runs with equal labels and k (exact: integers).  Holds
     host arrays only, so it pickles and loads where no GPU is visible."""
+
+    _table = property(lambda self: self.counts)
+    _norm = property(lambda self: self.S)
 
     def __init__(self, labels, counts, S, k):
         self.labels = list(labels)
@@ -270,44 +325,12 @@ class CompositionHistogram:
         self.S, self.k = int(S), int(k)
         assert self.counts.shape == (len(self.labels), self.k + 1)
 
-    def __len__(self):
-        return len(self.labels)
-
     def __add__(self, other):
         if not isinstance(other, CompositionHistogram):
             return NotImplemented
         if other.labels != self.labels or other.k != self.k:
             raise ValueError("composition histograms over different groups or panel sizes")
         return CompositionHistogram(self.labels, self.counts + other.counts, self.S + other.S, self.k)
-
-    def probabilities(self):
-        """P(a panel holds c members), float64[G, k+1] = counts / S."""
-        return self.counts / self.S
-
-    def mean(self):
-        """Expected members per panel (by linearity also the sum of the members' marginals)."""
-        return (self.counts * np.arange(self.k + 1, dtype=np.int64)).sum(axis=1) / self.S
-
-    def panel_share(self):
-        """mean / k: the panel share plot_intersectional_representation reports."""
-        return self.mean() / self.k
-
-    def variance(self):
-        """Variance of the members per panel (population form: the S panels are the distribution)."""
-        d = np.arange(self.k + 1, dtype=np.float64)[None, :] - self.mean()[:, None]
-        return (self.counts * d * d).sum(axis=1) / self.S
-
-    def prob_absent(self):
-        """P(a panel holds no member of the group)."""
-        return self.counts[:, 0] / self.S
-
-    def support(self):
-        """(lowest, highest) non-empty bin per group, int64[G] each; (-1, -1) for a run of no panels."""
-        nz = self.counts != 0
-        some = nz.any(axis=1)
-        lo = np.where(some, nz.argmax(axis=1), -1)
-        hi = np.where(some, self.k - nz[:, ::-1].argmax(axis=1), -1)
-        return lo.astype(np.int64), hi.astype(np.int64)
 
 
 def _is_device_tensor(a):
@@ -320,14 +343,12 @@ def group_hist_device(d_panels, S, W, d_masks, G, bins, d_hist, d_status, stream
                                          N.ptr(d_hist), N.ptr(d_status), ctypes.c_void_p(stream.cuda_stream)))
 
 
-def group_composition(groups, panels, k, stream=None):
-    """Composition of ``panels`` (packed host uint64[S, W], or the device tensor a run kept: int64 /
-    uint64 words, S*W of them) over ``groups``: a CompositionHistogram with k + 1 bins per group.  With
-    a HIP device the table comes from csa_group_hist_async (on ``stream``, default the panels' current
-    stream; one host copy of the table and the status); without one, from ``group_hist_host``.  A
-    panel holding more than k members of a group raises CsaError(CSA_E_INVALID) on either path."""
-    k, G, W = int(k), len(groups), groups.W
-    bins = k + 1
+@contextlib.contextmanager
+def _composition_input(panels, W, stream):
+    """The two composition calls' preamble.  Yields (panels, their number, stream).  Host panels where no HIP
+    device is visible come back as uint64[S, W] with stream None: the caller takes its numpy path.  Otherwise host
+    rows are uploaded, a tensor that is no whole number of W-word rows is refused, and the block runs on the panels'
+    device with ``stream`` (default: its current stream) current: it enqueues there and makes the one host copy."""
     on_device = _is_device_tensor(panels)
     if not on_device:
         panels = np.ascontiguousarray(panels, np.uint64).reshape(-1, W)
@@ -337,7 +358,8 @@ def group_composition(groups, panels, k, stream=None):
         except ImportError:
             have = False
         if not have:
-            return CompositionHistogram(groups.labels, group_hist_host(groups.masks, panels, bins), len(panels), k)
+            yield panels, len(panels), None
+            return
     import torch
     dev = panels.device if on_device else torch.device("cuda", torch.cuda.current_device())
     with torch.cuda.device(dev):
@@ -347,17 +369,27 @@ def group_composition(groups, panels, k, stream=None):
                 panels = torch.from_numpy(panels.view(np.int64).reshape(-1)).to(dev)
             if panels.numel() % W:
                 raise ValueError("panels: %d words are no whole number of W = %d" % (panels.numel(), W))
-            S = panels.numel() // W
-            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
-            out = torch.zeros(G * bins + 4, dtype=torch.int64, device=dev)
-            status = torch.zeros(4, dtype=torch.int32, device=dev)
-            group_hist_device(panels, S, W, d_masks, G, bins, out, status, st)
-            out[G * bins:].copy_(status)
-            h = out.cpu().numpy()                      # the call's one host wait
-    words = (h[G * bins:] & 0xFFFFFFFF).astype(np.uint32)
-    if words[0]:
-        N.check(N.lib().csa_status_decode(N.ptr(words)))
-    return CompositionHistogram(groups.labels, h[:G * bins].reshape(G, bins).copy(), S, k)
+            yield panels, panels.numel() // W, st
+
+
+def group_composition(groups, panels, k, stream=None):
+    """Composition of ``panels`` (packed host uint64[S, W], or the device tensor a run kept: int64 /
+    uint64 words, S*W of them) over ``groups``: a CompositionHistogram with k + 1 bins per group.  With
+    a HIP device the table comes from csa_group_hist_async (on ``stream``, default the panels' current
+    stream; one host copy of the table and the status); without one, from ``group_hist_host``.  A
+    panel holding more than k members of a group raises CsaError(CSA_E_INVALID) on either path."""
+    k, G, W = int(k), len(groups), groups.W
+    bins = k + 1
+    with _composition_input(panels, W, stream) as (panels, S, st):
+        if st is None:
+            return CompositionHistogram(groups.labels, group_hist_host(groups.masks, panels, bins), S, k)
+        import torch
+        from .device import StatusBlock
+        out = StatusBlock([("table", max(G * bins, 1))], torch.int64, panels.device, zero=True)
+        group_hist_device(panels, S, W, groups.device_masks(panels.device), G, bins, out.views["table"], out.status, st)
+        h, words = out.host()                      # the call's one host wait
+    N.raise_status(words)
+    return CompositionHistogram(groups.labels, h["table"][:G * bins].reshape(G, bins).copy(), S, k)
 
 
 # ---- weighted composition: the same question for a LEXIMIN / XMIN portfolio ------------------------
@@ -410,50 +442,21 @@ def group_whist_host(masks, panels, weights, bins, out=None):
     return out
 
 
-class WeightedCompositionHistogram:
+class WeightedCompositionHistogram(_Composition):
     """``values[g][c]`` = summed weight of the portfolio's panels holding exactly c members of group g
     (host float64[G, k+1], the raw table, each entry added in portfolio order), over ``P`` panels of
     size ``k``; ``total`` is the portfolio-order sum of the weights from ``0.``.  The derived
     quantities describe the distribution ``values / total`` and mean what CompositionHistogram's do.
     Holds host arrays only, so it pickles and loads where no GPU is visible."""
 
+    _table = property(lambda self: self.values)
+    _norm = property(lambda self: self.total)
+
     def __init__(self, labels, values, total, P, k):
         self.labels = list(labels)
         self.values = np.ascontiguousarray(values, np.float64)
         self.total, self.P, self.k = float(total), int(P), int(k)
         assert self.values.shape == (len(self.labels), self.k + 1)
-
-    def __len__(self):
-        return len(self.labels)
-
-    def probabilities(self):
-        """P(the drawn panel holds c members), float64[G, k+1] = values / total."""
-        return self.values / self.total
-
-    def mean(self):
-        """Expected members on the panel (by linearity also the sum of the members' marginals)."""
-        return (self.values * np.arange(self.k + 1, dtype=np.float64)).sum(axis=1) / self.total
-
-    def panel_share(self):
-        """mean / k: the panel share plot_intersectional_representation reports."""
-        return self.mean() / self.k
-
-    def variance(self):
-        """Variance of the members on the panel under the portfolio's distribution."""
-        d = np.arange(self.k + 1, dtype=np.float64)[None, :] - self.mean()[:, None]
-        return (self.values * d * d).sum(axis=1) / self.total
-
-    def prob_absent(self):
-        """P(the drawn panel holds no member of the group)."""
-        return self.values[:, 0] / self.total
-
-    def support(self):
-        """(lowest, highest) bin of non-zero weight per group, int64[G] each; (-1, -1) where there is none."""
-        nz = self.values != 0
-        some = nz.any(axis=1)
-        lo = np.where(some, nz.argmax(axis=1), -1)
-        hi = np.where(some, self.k - nz[:, ::-1].argmax(axis=1), -1)
-        return lo.astype(np.int64), hi.astype(np.int64)
 
 
 def portfolio_total(weights):
@@ -494,42 +497,21 @@ def portfolio_group_composition(groups, panels, weights, k, stream=None):
     bins = k + 1
     weights = np.ascontiguousarray(weights, np.float64).reshape(-1)
     total = portfolio_total(weights)
-    on_device = _is_device_tensor(panels)
-    if not on_device:
-        panels = np.ascontiguousarray(panels, np.uint64).reshape(-1, W)
-        try:
-            import torch
-            have = torch.cuda.is_available()
-        except ImportError:
-            have = False
-        if not have:
-            if len(panels) != len(weights):
-                raise ValueError("%d panels with %d weights" % (len(panels), len(weights)))
+    with _composition_input(panels, W, stream) as (panels, P, st):
+        if P != len(weights):
+            raise ValueError("%d panels with %d weights" % (P, len(weights)))
+        if st is None:
             return WeightedCompositionHistogram(groups.labels, group_whist_host(groups.masks, panels, weights, bins),
-                                                total, len(panels), k)
-    import torch
-    dev = panels.device if on_device else torch.device("cuda", torch.cuda.current_device())
-    with torch.cuda.device(dev):
-        st = stream or torch.cuda.current_stream(dev)
-        with torch.cuda.stream(st):
-            if not on_device:
-                panels = torch.from_numpy(panels.view(np.int64).reshape(-1)).to(dev)
-            if panels.numel() % W:
-                raise ValueError("panels: %d words are no whole number of W = %d" % (panels.numel(), W))
-            P = panels.numel() // W
-            if P != len(weights):
-                raise ValueError("%d panels with %d weights" % (P, len(weights)))
-            d_masks = torch.from_numpy(groups.masks.view(np.int64).reshape(-1)).to(dev)
-            d_w = torch.from_numpy(weights).to(dev)
-            out = torch.empty(G * bins + 2, dtype=torch.float64, device=dev)   # table, then the status words
-            status = out[G * bins:].view(torch.int32)
-            status.zero_()
-            group_whist_device(panels, P, W, d_w, d_masks, G, bins, out, status, st)
-            h = out.cpu().numpy()                      # the call's one host wait
-    words = h[G * bins:].view(np.uint32)
-    if words[0]:
-        N.check(N.lib().csa_status_decode(N.ptr(np.ascontiguousarray(words))))
-    return WeightedCompositionHistogram(groups.labels, h[:G * bins].reshape(G, bins).copy(), total, P, k)
+                                                total, P, k)
+        import torch
+        from .device import StatusBlock
+        d_masks = groups.device_masks(panels.device)
+        d_w = torch.from_numpy(weights).to(panels.device)
+        out = StatusBlock([("table", max(G * bins, 1))], torch.float64, panels.device)
+        group_whist_device(panels, P, W, d_w, d_masks, G, bins, out.views["table"], out.status, st)
+        h, words = out.host()                      # the call's one host wait
+    N.raise_status(words)
+    return WeightedCompositionHistogram(groups.labels, h["table"][:G * bins].reshape(G, bins).copy(), total, P, k)
 
 
 # ---- panel multiplicities: the run as a distribution over whole panels -----------------------------
