@@ -102,6 +102,10 @@ SIGNATURES = {
     "csa_exchange_keys_async": (ctypes.c_int, [_P, _P, _U64, _I32, _U64, _U32, _U64, _P, _U64, _P, _P, _P, _P]),
     "csa_unique_keys_scratch_bytes": (_U64, [_U64, _I32]),
     "csa_unique_keys_async": (ctypes.c_int, [_P, _I32, _U64, _U32, _P, _U32, _U64, _P, _P, _U64, _P, _P, _P]),
+    "csa_exchange_mult_keys_async": (ctypes.c_int, [_P, _U64, _P, _P, _P, _U64, _U32, _U64, _P, _P, _P, _P]),
+    "csa_merge_mult_keys_scratch_bytes": (_U64, [_U64, _I32]),
+    "csa_merge_mult_keys_async": (ctypes.c_int, [_P, _I32, _U64, _U32, _P, _U32, _U64, _P, _P, _U64, _P, _P, _P, _P,
+                                                 _P]),
 }
 
 _lib = None

@@ -746,12 +746,13 @@ def legacy_panel_distribution(instance: Instance, iterations: int, random_seed: 
     length must equal ``len(found_panels)`` and the multiplicities must sum to ``iterations``:
     RuntimeError otherwise.  ``rng="mt"`` runs the same passes over the host-drawn panels.  With
     ``keep_panels=False`` the spectrum and estimators work; ``top`` / ``count`` raise.  Sharded runs
-    are not offered: with torch.distributed initialised and world size > 1 the call raises
-    NotImplementedError (the counts would have to travel with the exchange's 24-byte keys)."""
+    are the sibling's: with torch.distributed initialised and world size > 1 this call raises
+    NotImplementedError and ``distributed.legacy_panel_distribution_distributed`` is the call to make (the
+    counts travel with the exchange's keys, 32 bytes each)."""
     from . import distributed as D
     if D.world_size() > 1:
-        raise NotImplementedError("legacy_panel_distribution: sharded runs (world size %d) are not supported"
-                                  % D.world_size())
+        raise NotImplementedError("legacy_panel_distribution: sharded runs (world size %d) are not supported here; "
+                                  "call distributed.legacy_panel_distribution_distributed" % D.world_size())
     run = _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, None, multiplicity=True)
     return run.alloc, run.panels, run.histogram, run.distribution
 

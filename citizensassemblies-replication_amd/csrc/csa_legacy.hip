@@ -1525,6 +1525,7 @@ __global__ __launch_bounds__(256) void pair_histogram_kernel(const int64_t *__re
 constexpr int kMaxWorld = 1024;
 constexpr int kXbThreads = 256;
 constexpr uint64_t kExchangeOverflow = 0xFFFFFFFFFFFFFFFEull;  // status "panel" of a full segment
+constexpr uint64_t kMultOverflow = 0xFFFFFFFFFFFFFFFDull;      // status "panel": a merged multiplicity beyond uint32
 __global__ __launch_bounds__(kXbThreads) void exchange_bucket_kernel(
     const uint64_t *__restrict__ hashes, const uint64_t *__restrict__ panels, int W, const uint32_t *__restrict__ rep,
     const unsigned long long *__restrict__ rep_count, uint32_t world, uint64_t capacity,
@@ -2635,6 +2636,8 @@ int csa_status_decode(const uint32_t *h) {
                 return fail(CSA_E_UNSUPPORTED, "distinct-panel exchange: an owner segment exceeded its capacity");
             if (panel == 0xFFFFFFFFFFFFFFFFull)
                 return fail(CSA_E_UNSUPPORTED, "distinct panels: a partition exceeded its LDS table");
+            if (panel == kMultOverflow)
+                return fail(CSA_E_UNSUPPORTED, "panel multiplicities: a merged count or index exceeds 32 bits");
             return fail(CSA_E_UNSUPPORTED, "device status %u at panel %llu", h[0], (unsigned long long)panel);
         default:
             return fail((int)h[0], "device status %u at panel %llu", h[0], (unsigned long long)panel);
@@ -3626,6 +3629,90 @@ int csa_legacy_attempt(csa_instance *I, int32_t k, uint64_t seed, uint64_t panel
     if (sel_out) HIPCHK(hipMemcpy(sel_out, sel.p, I->F * 4, hipMemcpyDeviceToHost));
     if (rem_out) HIPCHK(hipMemcpy(rem_out, rem.p, I->F * 4, hipMemcpyDeviceToHost));
     if (present_out) HIPCHK(hipMemcpy(present_out, present.p, I->W * 8, hipMemcpyDeviceToHost));
+    return CSA_OK;
+}
+
+}  // extern "C"
+
+// The 32-byte exchange stands last in the file, kernels (templates, see the .inc's "Layout") and entry
+// points, so that every kernel above keeps the offset in the code object it had before these were added.
+namespace {
+#include "multiplicity_exchange.inc"
+}  // namespace
+
+extern "C" {
+
+// The 32-byte exchange (multiplicity_exchange.inc): keys (h1, h2, global first index, multiplicity).
+int csa_exchange_mult_keys_async(const uint64_t *d_hashes, uint64_t n_panels, const uint32_t *d_first,
+                                 const uint32_t *d_mult, const uint64_t *d_distinct, uint64_t panel_begin,
+                                 uint32_t world, uint64_t capacity, uint64_t *d_send_keys, uint64_t *d_send_counts,
+                                 uint32_t *d_status, void *stream) {
+    if (world == 0 || world > (uint32_t)kMaxWorld || capacity == 0 || !d_send_keys || !d_send_counts || !d_status ||
+        !d_distinct)
+        return fail(CSA_E_INVALID, "exchange mult keys: bad arguments");
+    if (n_panels && (!d_hashes || !d_first || !d_mult))
+        return fail(CSA_E_INVALID, "exchange mult keys: NULL pointer with %llu panels", (unsigned long long)n_panels);
+    if (n_panels >= (1ull << 32) || panel_begin > (1ull << 32) - n_panels)
+        return fail(CSA_E_UNSUPPORTED, "exchange mult keys: panel_begin + n_panels > 2^32 (u32 indices)");
+    const hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(d_send_counts, 0, (size_t)world * 8, st));
+    if (n_panels == 0) return CSA_OK;
+    const unsigned grid = (unsigned)((n_panels + kXbThreads - 1) / kXbThreads);
+    hipLaunchKernelGGL(mult_keys_kernel<>, dim3(grid), dim3(kXbThreads), 0, st, d_hashes, n_panels, d_first, d_mult,
+                       reinterpret_cast<const unsigned long long *>(d_distinct), panel_begin, world, capacity,
+                       d_send_keys, reinterpret_cast<unsigned long long *>(d_send_counts), d_status);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+uint64_t csa_merge_mult_keys_scratch_bytes(uint64_t n_keys, int32_t W) { return 8 * mkey_layout(n_keys, W).words; }
+
+int csa_merge_mult_keys_async(const csa_instance *I, int32_t k, uint64_t seed, uint32_t max_attempts,
+                              const uint64_t *d_keys, uint32_t n_segments, uint64_t capacity,
+                              const uint64_t *d_seg_counts, void *d_scratch, uint64_t scratch_bytes, uint32_t *d_first,
+                              uint32_t *d_mult, uint64_t *d_distinct, uint32_t *d_status, void *stream) {
+    if (!I || !d_keys || !d_seg_counts || !d_scratch || !d_first || !d_mult || !d_distinct || !d_status ||
+        capacity == 0 || capacity > 0xFFFFFFFFull || n_segments == 0)
+        return fail(CSA_E_INVALID, "merge mult keys: bad arguments");
+    const uint64_t total = (uint64_t)n_segments * capacity;
+    if (total >= (1ull << 32)) return fail(CSA_E_UNSUPPORTED, "merge mult keys: n_segments * capacity >= 2^32");
+    const int W = I->W;
+    const MkeyLayout L = mkey_layout(total, W);
+    if (scratch_bytes < 8 * L.words)
+        return fail(CSA_E_INVALID, "merge mult keys: scratch_bytes < csa_merge_mult_keys_scratch_bytes");
+    uint64_t *base = static_cast<uint64_t *>(d_scratch);
+    auto ull = [&](uint64_t off) { return reinterpret_cast<unsigned long long *>(base + off); };
+    unsigned long long *list_len = ull(L.list_len), *out_len = reinterpret_cast<unsigned long long *>(d_distinct);
+    uint64_t *list = base + L.list, *cand = base + L.cand, *rows = base + L.rows;
+    const hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(base, 0, L.zero_words * 8, st));
+    HIPCHK(hipMemsetAsync(base + L.acc_f, 0xFF, L.ones_words * 8, st));
+    HIPCHK(hipMemsetAsync(d_first, 0, total * 4, st));  // entries past the list hold zero
+    HIPCHK(hipMemsetAsync(d_mult, 0, total * 4, st));
+    HIPCHK(hipMemsetAsync(out_len, 0, 8, st));
+    const unsigned grid = (unsigned)((total + 255) / 256);
+    hipLaunchKernelGGL(mkey_insert_kernel<>, dim3(grid), dim3(256), 0, st, d_keys, total, (uint32_t)capacity, d_seg_counts,
+                       ull(L.table), L.slots - 1, ull(L.acc_m), ull(L.acc_f), list, cand, list_len, total, d_status);
+    HIPCHK(hipGetLastError());
+    // re-draw the listed panels (a persistent index-list draw: workgroups past the list leave at once)
+    DrawRequest rq;
+    rq.a.k = k, rq.a.seed = seed, rq.a.n_panels = 2 * total, rq.a.max_attempts = max_attempts;
+    rq.a.panel_list = list, rq.a.n_panels_dev = list_len;
+    rq.a.panels = rows, rq.a.status = d_status;
+    rq.stream = st;
+    int rc = launch_draw(I, rq);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mkey_merge_kernel<>, dim3(grid), dim3(256), 0, st, d_keys, (const uint64_t *)rows, W,
+                       (const uint64_t *)cand, (const unsigned long long *)list_len, total, ull(L.acc_m), ull(L.acc_f),
+                       ull(L.table2), L.slots - 1, ull(L.acc2_m), ull(L.acc2_f));
+    const unsigned egrid = (unsigned)((L.slots + kMeThreads * kMeSlots - 1) / (kMeThreads * kMeSlots));
+    hipLaunchKernelGGL(mkey_emit_kernel<>, dim3(egrid), dim3(kMeThreads), 0, st, (const unsigned long long *)ull(L.table),
+                       (const unsigned long long *)ull(L.acc_m), (const unsigned long long *)ull(L.acc_f), L.slots, total,
+                       d_first, d_mult, out_len, d_status);
+    hipLaunchKernelGGL(mkey_emit_kernel<>, dim3(egrid), dim3(kMeThreads), 0, st, (const unsigned long long *)ull(L.table2),
+                       (const unsigned long long *)ull(L.acc2_m), (const unsigned long long *)ull(L.acc2_f), L.slots,
+                       total, d_first, d_mult, out_len, d_status);
+    HIPCHK(hipGetLastError());
     return CSA_OK;
 }
 

@@ -147,6 +147,81 @@ def distinct_segments(hashes, panels, counts):
     return distinct_exact(hv, pv)
 
 
+def _local_multiplicities(h, p):
+    """Host mirror of csa_unique_mult_async: per distinct (hash, bitmask) row of uint64[m, 2] / uint64[m, W]
+    its lowest index and its number of copies, ascending in the index (int64 each)."""
+    if len(h) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    _, first, mult = np.unique(np.concatenate([h, p], axis=1), axis=0, return_index=True, return_counts=True)
+    order = np.argsort(first, kind="stable")
+    return first[order].astype(np.int64), mult[order].astype(np.int64)
+
+
+def mult_key_buckets(hashes, panels, panel_begin, world, cap):
+    """Host mirror of csa_unique_mult_async + csa_exchange_mult_keys_async (hashes uint64[m, 2], panels
+    uint64[m, W], this rank's, global indices from ``panel_begin``): one 32-byte key (h1, h2, panel_begin
+    + first local index, local multiplicity) per local distinct panel, in fixed-capacity owner segments
+    (h1 % world).  Returns (uint64[world, cap, 4], int64[world] counts); a segment past ``cap`` raises."""
+    h = np.asarray(hashes, np.uint64).reshape(-1, 2)
+    p = np.asarray(panels, np.uint64)
+    assert p.ndim == 2 and len(p) == len(h)
+    first, mult = _local_multiplicities(h, p)
+    keys = np.zeros((world, cap, 4), np.uint64)
+    sc = np.zeros(world, np.int64)
+    owner = (h[first, 0] % np.uint64(world)).astype(np.int64)
+    for w in range(world):
+        sel = np.nonzero(owner == w)[0]
+        if len(sel) > cap:
+            raise RuntimeError("panel-multiplicity exchange: %d panels for owner %d exceed the segment capacity %d"
+                               % (len(sel), w, cap))
+        keys[w, : len(sel), :2] = h[first[sel]]
+        keys[w, : len(sel), 2] = (first[sel] + int(panel_begin)).astype(np.uint64)
+        keys[w, : len(sel), 3] = mult[sel].astype(np.uint64)
+        sc[w] = len(sel)
+    return keys, sc
+
+
+def merge_mult_keys(keys, counts, panels_of):
+    """Host mirror of csa_merge_mult_keys_async: the valid leading keys of each segment (uint64[segments, cap,
+    4], counts[segments]) merged into one entry per distinct panel -- equal 128-bit hash AND equal bitmask;
+    multiplicity = the sum of the keys', first = the lowest of their global indices.  ``panels_of(global
+    indices)`` -> uint64[len, W] stands for the owner's re-draw and is asked only for keys whose hash occurs
+    more than once.  Returns (first int64[u], mult int64[u]) ascending in first."""
+    k = np.asarray(keys, np.uint64)
+    c = [int(x) for x in counts]
+    v = np.concatenate([k[s, : c[s]] for s in range(len(c))]) if c else np.zeros((0, 4), np.uint64)
+    if len(v) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    _, group, size = np.unique(v[:, :2], axis=0, return_inverse=True, return_counts=True)
+    group = group.reshape(-1)
+    shared = np.nonzero(size[group] > 1)[0]
+    label = np.stack([group.astype(np.int64), np.zeros(len(v), np.int64)], axis=1)
+    if len(shared):
+        rows = np.ascontiguousarray(panels_of(v[shared, 2].astype(np.int64)), np.uint64).reshape(len(shared), -1)
+        _, which = np.unique(rows, axis=0, return_inverse=True)
+        label[shared, 1] = which.reshape(-1) + 1
+    _, entry = np.unique(label, axis=0, return_inverse=True)
+    entry = entry.reshape(-1)
+    u = int(entry.max()) + 1
+    mult = np.zeros(u, np.int64)
+    np.add.at(mult, entry, v[:, 3].astype(np.int64))
+    first = np.full(u, np.iinfo(np.int64).max, np.int64)
+    np.minimum.at(first, entry, v[:, 2].astype(np.int64))
+    order = np.argsort(first, kind="stable")
+    return first[order], mult[order]
+
+
+def mult_record(mult, n_bins):
+    """Host mirror of csa_mult_spectrum_async's record over a list's multiplicities: int64 [length |
+    spectrum[n_bins] | entries >= n_bins, max, sum m^2, sum m]."""
+    m = np.asarray(mult, np.int64)
+    out = np.zeros(1 + n_bins + 4, np.int64)
+    out[0] = len(m)
+    out[1:1 + n_bins] = np.bincount(m[m < n_bins], minlength=n_bins)
+    out[1 + n_bins:] = [int((m >= n_bins).sum()), int(m.max()) if len(m) else 0, int((m * m).sum()), int(m.sum())]
+    return out
+
+
 class HashTable:
     """Reusable device table + count for csa_unique_async (grows on demand)."""
 
@@ -284,6 +359,101 @@ class PanelExchange:
                                             N.ptr(self.table.count), N.ptr(status), sp_))
         with torch.cuda.stream(st):
             return self.table.count.clone()
+
+
+    # ---- the 32-byte exchange: the panel multiplicities travel with the keys --------------------
+    def _mult_buffers(self, n_bins):
+        """The buffers of run_multiplicity, sized once for this exchange (and one spectrum width)."""
+        import torch
+        from . import _native as N
+        b = getattr(self, "_mult", None)
+        if b is not None and b["n_bins"] == n_bins:
+            return b
+        L, dev, seg = N.lib(), self.device, self.world * self.cap
+        i64, i32 = torch.int64, torch.int32
+        lb = int(L.csa_unique_mult_scratch_bytes(self.n_local))
+        ob = int(L.csa_merge_mult_keys_scratch_bytes(seg, self.W))
+        b = self._mult = {
+            "n_bins": n_bins,
+            "local_scratch": torch.empty((lb + 7) // 8, dtype=i64, device=dev),
+            "local_first": torch.empty(self.n_local, dtype=i32, device=dev),
+            "local_mult": torch.empty(self.n_local, dtype=i32, device=dev),
+            "local_len": torch.zeros(1, dtype=i64, device=dev),
+            "send_k": torch.empty(4 * seg, dtype=i64, device=dev),
+            "recv_k": torch.empty(4 * seg, dtype=i64, device=dev),
+            "owner_scratch": torch.empty((ob + 7) // 8, dtype=i64, device=dev),
+            "first": torch.empty(seg, dtype=i32, device=dev),
+            "mult": torch.empty(seg, dtype=i32, device=dev),
+            "record": torch.zeros(1 + n_bins + 4, dtype=i64, device=dev),
+        }
+        return b
+
+    def run_multiplicity(self, hashes, panels, n, status=None, stream=None, panel_begin=0, redraw=None, n_bins=4096,
+                         panels_of=None):
+        """The exchange in which the counts travel.  This rank's (first, multiplicity) list
+        (csa_unique_mult_async -- the local dedupe, run once) goes out as 32-byte keys (h1, h2, global first
+        index, multiplicity) to the hashes' owners (csa_exchange_mult_keys_async, two equal-split
+        all_to_alls: counts and keys); the owner merges what it received (csa_merge_mult_keys_async,
+        re-drawing hash-matched keys with ``redraw`` = (instance, k, seed, max_attempts)) and takes the
+        spectrum of its list (csa_mult_spectrum_async, ``n_bins`` bins).
+
+        Returns (first, mult, record): the owner's list -- the panels whose h1 % world is this rank, int32
+        tensors of world * cap uint32 words, zero past the list -- and int64 [length | spectrum[n_bins] |
+        overflow, max, sum m^2, sum m].  All three are buffers of the exchange, overwritten by its next run.
+        Device inputs: nothing waits.  Host tensors run the numpy mirrors (mult_key_buckets, merge_mult_keys
+        with ``panels_of(global indices)`` for the re-draw) and return int64 tensors of the list's length."""
+        import torch
+        n, n_bins = int(n), int(n_bins)
+        assert n <= self.n_local
+        if not hashes.is_cuda:
+            import torch.distributed as dist
+            keys, sc = mult_key_buckets(hashes.numpy().view(np.uint64)[: 2 * n].reshape(n, 2),
+                                        panels.numpy().view(np.uint64)[: n * self.W].reshape(n, self.W),
+                                        panel_begin, self.world, self.cap)
+            rk, rc = (torch.empty(x.shape, dtype=torch.int64) for x in (keys, sc))
+            dist.all_to_all_single(rc, torch.from_numpy(sc))
+            dist.all_to_all_single(rk, torch.from_numpy(keys.view(np.int64)))
+            first, mult = merge_mult_keys(rk.numpy().view(np.uint64), rc.numpy(), panels_of)
+            return torch.from_numpy(first), torch.from_numpy(mult), torch.from_numpy(mult_record(mult, n_bins))
+        from . import _native as N
+        assert status is not None, "the device exchange reports a full segment in the status block"
+        assert self.redraw is not None, "the multiplicity exchange re-draws: build the exchange with redraw="
+        handle, k, seed, max_att = redraw if redraw is not None else self.redraw
+        st = stream or torch.cuda.current_stream(hashes.device)
+        sp_ = ctypes.c_void_p(st.cuda_stream)
+        L = N.lib()
+        with torch.cuda.stream(st):
+            b = self._mult_buffers(n_bins)
+        rec = b["record"]
+        N.check(L.csa_unique_mult_async(N.ptr(hashes), N.ptr(panels), n, self.W, N.ptr(b["local_scratch"]),
+                                        b["local_scratch"].numel() * 8, N.ptr(b["local_first"]), N.ptr(b["local_mult"]),
+                                        N.ptr(b["local_len"]), N.ptr(status), sp_))
+        N.check(L.csa_exchange_mult_keys_async(N.ptr(hashes), n, N.ptr(b["local_first"]), N.ptr(b["local_mult"]),
+                                               N.ptr(b["local_len"]), int(panel_begin), self.world, self.cap,
+                                               N.ptr(b["send_k"]), N.ptr(self.send_c), N.ptr(status), sp_))
+        with torch.cuda.stream(st):
+            _all_to_all(self.recv_c, self.send_c)
+            _all_to_all(b["recv_k"], b["send_k"])
+        N.check(L.csa_merge_mult_keys_async(handle, int(k), int(seed) & M64, int(max_att), N.ptr(b["recv_k"]),
+                                            self.world, self.cap, N.ptr(self.recv_c), N.ptr(b["owner_scratch"]),
+                                            b["owner_scratch"].numel() * 8, N.ptr(b["first"]), N.ptr(b["mult"]),
+                                            N.ptr(rec), N.ptr(status), sp_))
+        N.check(L.csa_mult_spectrum_async(N.ptr(b["mult"]), N.ptr(rec), self.world * self.cap, N.ptr(rec[1:]), n_bins,
+                                          N.ptr(rec[1 + n_bins:]), sp_))
+        return b["first"], b["mult"], rec
+
+
+def _all_gather(out, inp):
+    """all_gather of equal 1-D tensors into ``out`` (world * len), through host copies for a gloo rehearsal
+    on device tensors."""
+    import torch.distributed as dist
+    if _host_collectives(inp) or not inp.is_cuda:
+        parts = list(out.cpu().split(inp.numel()))
+        dist.all_gather(parts, inp.cpu())
+        import torch
+        out.copy_(torch.cat(parts))
+    else:
+        dist.all_gather_into_tensor(out, inp)
 
 
 def _all_reduce_pairs(pairs, pair_bound, stream):
@@ -460,7 +630,7 @@ def shard_device():
 
 
 def legacy_probabilities_distributed(instance, iterations, random_seed, keep_panels=True, chunk=None,
-                                     timings=None, groups=None):
+                                     timings=None, groups=None, multiplicity=False, top_keep=64):
     """analysis.py:162-191 with the panels sharded over the ranks of the default group.  Every rank
     returns the whole job's alloc, pair histogram and exact distinct-panel count.
 
@@ -483,7 +653,16 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
     times in ms.  ``groups`` (a stats.GroupSet; analysis.legacy_composition's sharded form): every rank
     runs group_hist_kernel over its share and the tables are summed in one more all_reduce; the call
     then returns a fourth value, the CompositionHistogram of the whole job on every rank -- never a
-    share's."""
+    share's.
+
+    ``multiplicity`` (``legacy_panel_distribution_distributed``): the run also returns, last, its
+    stats.PanelDistribution.  With an exchange the 32-byte one (PanelExchange.run_multiplicity) runs in
+    place of the 24-byte one -- the distinct count is the sum of the owners' list lengths -- the owners'
+    spectra and sums ride in the same all_reduce(SUM), the maximum in the MAX reduce beside the status
+    code, and each owner's ``top_keep`` most frequent entries are gathered to every rank; all of it comes
+    back in the one host copy.  Only a global maximum of MULT_BINS or more costs a second spectrum pass,
+    all_reduce and copy, on every rank alike.  Without an exchange the one-GPU passes run
+    (stats.unique_mult_device), as in analysis.legacy_sample_device."""
     import time
     import torch
     import torch.distributed as dist
@@ -492,6 +671,10 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
     t0 = time.perf_counter()
     world, r = world_size(), rank()
     S = int(iterations)
+    if multiplicity and S >= 1 << 32:     # the same on every rank, before any collective
+        raise ValueError("panel multiplicities: %d draws do not fit the lists' 32-bit counts and indices" % S)
+    top_keep = max(0, int(top_keep))
+    mb = A.MULT_BINS
     A.seed(random_seed)
     A.STREAM.take_panels(S)
     enc = A.encode_cached(instance.categories, instance.agents)
@@ -515,8 +698,10 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
             hashes = torch.empty(max(2 * local, 2), dtype=torch.int64, device=dev)
             pairs = torch.empty(n * n, dtype=torch.int64, device=dev)
             # [counts (n) | attempts, SelectionErrors, rejections | distinct count]: one all_reduce(SUM)
-            acc = torch.zeros(n + 4, dtype=torch.int64, device=dev)
-            d_counts, d_stats, d_unique = acc.split([n, 3, 1])
+            # (a multiplicity run through the exchange: | spectrum[mb] | overflow, sum m^2, sum m)
+            sharded_mult = multiplicity and ex is not None
+            acc = torch.zeros(n + 4 + (mb + 3 if sharded_mult else 0), dtype=torch.int64, device=dev)
+            d_counts, d_stats, d_unique = acc[:n + 4].split([n, 3, 1])
             pipe.reset(pairs=False)
             A.reset_draw_stats(enc, st)
             # one rank: its distinct-count table before the draws (analysis.distinct_table)
@@ -541,16 +726,34 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
                 # error -- the exchange writes its own status only past a full segment, and the first
                 # error recorded in a block wins (csa_status_decode)
                 _all_reduce_pairs(pairs, S, st)
-                u = ex.run(hashes, panels, local, status=pipe.status, stream=st, panel_begin=begin,
-                           redraw=(enc.handle, k, random_seed, 0))
+                if multiplicity:
+                    o_first, o_mult, rec = ex.run_multiplicity(hashes, panels, local, status=pipe.status, stream=st,
+                                                               panel_begin=begin, n_bins=mb,
+                                                               redraw=(enc.handle, k, random_seed, 0))
+                    u = rec[:1]          # the owners' list lengths sum to the job's distinct count
+                    acc[n + 4:n + 4 + mb] = rec[1:1 + mb]
+                    acc[n + 4 + mb:n + 5 + mb] = rec[1 + mb:2 + mb]      # overflow | (max: below) | sum m^2, sum m
+                    acc[n + 5 + mb:] = rec[3 + mb:]
+                else:
+                    u = ex.run(hashes, panels, local, status=pipe.status, stream=st, panel_begin=begin,
+                               redraw=(enc.handle, k, random_seed, 0))
             else:
                 # one rank owns every panel: nothing to reduce, and the exact local distinct count runs on
                 # a side stream after the draws, beside the last chunk's counting and pairs
-                pipe.rejoin(pipe.distinct_count(table, hashes, panels, local,
-                                                (pipe.draw_stream if local else st).record_event()))
+                ust = pipe.distinct_count(table, hashes, panels, local,
+                                          (pipe.draw_stream if local else st).record_event())
+                if multiplicity:
+                    from .stats import unique_mult_device
+                    m_first, m_mult, m_out = unique_mult_device(hashes, panels, local, W, pipe.status, ust, mb)
+                    fields += zip(A.MULT_FIELDS, m_out.split([1, mb, 4]))
+                pipe.rejoin(ust)
                 u = table.count
             d_unique.copy_(u)
             code = pipe.status[:1].to(torch.int64)
+            if sharded_mult:
+                # [status code | the largest multiplicity]: one MAX reduce
+                red = torch.cat([code, rec[2 + mb:3 + mb]])
+                code = red[:1]
             if ex is not None:
                 _all_reduce(acc)
                 if groups is not None:
@@ -558,13 +761,29 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
                 # MAX over ranks of a priority key: a draw error (KeyError / attempt limit) on any rank
                 # outranks an exchange error on another (an overflowing segment), whatever their codes
                 code += ERR_DRAW_PRIORITY * ((code == N.CSA_E_NO_CANDIDATE) | (code == N.CSA_E_ATTEMPT_LIMIT))
-                _all_reduce(code, op=dist.ReduceOp.MAX)
+                _all_reduce(red if sharded_mult else code, op=dist.ReduceOp.MAX)
                 code %= ERR_DRAW_PRIORITY
+            if sharded_mult:
+                fields += [("mult_sums", acc[n + 4:]), ("mult_max", red[1:]), ("mult_owned", rec[:1])]
+                if top_keep:
+                    # each owner's top_keep best entries, to every rank: (multiplicity descending, first index
+                    # ascending) is a total order, so the job's top_keep lie in the union of the owners'
+                    best = _mult_order_keys(o_first, o_mult).topk(min(top_keep, o_mult.numel())).values
+                    gathered = torch.empty(world * best.numel(), dtype=torch.int64, device=dev)
+                    _all_gather(gathered, best)
+                    fields.append(("mult_top", gathered))
             h, words = pipe.host_fields(fields + [("code", code)])     # the one host wait
         t2 = time.perf_counter()
     agreed = int(h["code"][0])
     if agreed:
         _decode_status(words, agreed)
+    distribution = None
+    if multiplicity:
+        with torch.cuda.device(dev), torch.cuda.stream(st):
+            if sharded_mult:
+                distribution = _sharded_distribution(h, o_first, o_mult, rec, S, mb, top_keep, st)
+            else:
+                mult = A._multiplicity(h, m_first, m_mult, S, int(h["unique"][0]), st)
     stats = dict(zip(A.STAT_KEYS, (int(x) for x in h["stats"])))
     # one rank (no exchange): its panels are the whole run's, so found_panels keeps them on the device and
     # decodes them when iterated, as the one-GPU call does
@@ -576,8 +795,84 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
     if keep_panels and not solo:
         # nothing kept, nothing sent: the whole job's panels are re-drawn where they are read
         out[1]._redraw = PanelRedraw(device_redraw(enc, k, random_seed, dev), S, W, chunk=max(C, 1 << 16))
+    if multiplicity:
+        from .stats import PanelDistribution
+        if sharded_mult:
+            distribution.bind(out[1]._redraw if keep_panels else None, enc.n, enc.agent_ids)
+        else:
+            distribution = PanelDistribution(S, mult["first"], mult["mult"], raw.panels, enc.n, enc.agent_ids,
+                                             spectrum=mult["spectrum"], sum_squares=mult["sum_squares"])
+        out = out + (distribution,)
     if timings is not None:
         t3 = time.perf_counter()
         timings.update(setup_ms=(t1 - t0) * 1e3, device_ms=(t2 - t1) * 1e3, finish_ms=(t3 - t2) * 1e3,
                        total_ms=(t3 - t0) * 1e3)
     return out
+
+
+def _mult_order_keys(first, mult):
+    """int64 keys of a device (first, multiplicity) list (uint32 words) whose SIGNED order is multiplicity
+    descending-is-larger, then first index ascending-is-larger: (mult << 32 | ~first) with the sign bit
+    flipped.  Zero entries past the list give the smallest key of all."""
+    import torch
+    m32 = 0xFFFFFFFF
+    key = ((mult.to(torch.int64) & m32) << 32) | (m32 - (first.to(torch.int64) & m32))
+    return key ^ (-1 << 63)
+
+
+def mult_order_decode(keys):
+    """Host (first, mult) int64 arrays of _mult_order_keys' keys, the zero entries dropped, ordered by
+    multiplicity descending, then first index ascending."""
+    k = np.asarray(keys, np.int64).view(np.uint64) ^ np.uint64(1 << 63)
+    k = np.sort(k[(k >> np.uint64(32)) != 0])[::-1]
+    mult = (k >> np.uint64(32)).astype(np.int64)
+    first = (np.uint64(0xFFFFFFFF) - (k & np.uint64(0xFFFFFFFF))).astype(np.int64)
+    return first, mult
+
+
+def _sharded_distribution(h, o_first, o_mult, rec, S, mb, top_keep, stream):
+    """The whole job's stats.ShardedPanelDistribution from the call's host copy ``h`` (the reduced record)
+    and this rank's owner list (buffers of the exchange, ``rec`` its record: the list's entries are copied
+    out here, on ``stream``).  A global maximum of ``mb`` or more takes the spectrum again with max + 1
+    bins: every rank sees the same reduced maximum, so every rank enters the all_reduce."""
+    import torch
+    from . import _native as N
+    from .stats import ShardedPanelDistribution
+    over, sq, total = (int(x) for x in h["mult_sums"][mb:])
+    top, distinct, owned = int(h["mult_max"][0]), int(h["unique"][0]), int(h["mult_owned"][0])
+    spectrum = h["mult_sums"][:mb]
+    if total != S:
+        raise RuntimeError("panel multiplicities: the owners' lists sum to %d, the run drew %d panels" % (total, S))
+    if over or top >= mb:
+        out = torch.empty(top + 1 + 4, dtype=torch.int64, device=o_mult.device)
+        N.check(N.lib().csa_mult_spectrum_async(N.ptr(o_mult), N.ptr(rec), o_mult.numel(), N.ptr(out), top + 1,
+                                                N.ptr(out[top + 1:]), ctypes.c_void_p(stream.cuda_stream)))
+        _all_reduce(out)
+        spectrum = out.cpu().numpy()
+        if spectrum[top + 1] or int(spectrum[top + 4]) != S:
+            raise RuntimeError("panel multiplicities: the spectrum's second pass disagrees with its first")
+    cand = mult_order_decode(h["mult_top"]) if top_keep else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+    return ShardedPanelDistribution(S, distinct, spectrum[:top + 1].copy(), sq, o_first[:owned].clone(),
+                                    o_mult[:owned].clone(), cand, top_keep)
+
+
+def legacy_panel_distribution_distributed(instance, iterations, random_seed, keep_panels=True, chunk=None,
+                                          top_keep=64, timings=None):
+    """analysis.legacy_panel_distribution with the panels sharded over the ranks of the default group:
+    returns ``(alloc, found_panels, pair_histogram, panel_distribution)`` on every rank, the first three
+    equal, bit for bit, to what ``legacy_probabilities_distributed`` returns (the same body runs).
+
+    ``panel_distribution`` (a stats.ShardedPanelDistribution with an exchange -- more than one rank, or
+    CSA_FORCE_EXCHANGE=1 -- a stats.PanelDistribution over the device list otherwise) describes the WHOLE
+    job on every rank: S, distinct, spectrum, sum_squares, max_multiplicity and the estimators.  Each
+    rank counts its share once (csa_unique_mult_async), the counts travel with the exchange's keys (32
+    bytes: h1, h2, global first index, multiplicity) to the hash's owner, which merges them exactly
+    (csa_merge_mult_keys_async); the owners' spectra are summed in the call's all_reduce and each owner's
+    ``top_keep`` most frequent entries are gathered, all inside the call and its one host copy.
+    ``owned()`` is this rank's owner list; ``top(m)`` for m <= ``top_keep`` re-draws m panels by index on
+    this rank, alone; ``multiplicities()``, ``count()``, a longer ``top`` and pickling re-draw the job's
+    panels on this rank (distributed.PanelRedraw, as found_panels) and count them there -- no collective.
+    ``top_keep=0`` gathers nothing.  With ``keep_panels=False`` the estimators work and those raise.
+    Philox mode only: MT-mode runs are not sharded.  S < 2^32."""
+    return legacy_probabilities_distributed(instance, iterations, random_seed, keep_panels=keep_panels, chunk=chunk,
+                                            timings=timings, multiplicity=True, top_keep=top_keep)

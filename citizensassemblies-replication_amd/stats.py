@@ -717,6 +717,112 @@ class PanelDistribution:
         self.max_multiplicity = len(self.spectrum) - 1
 
 
+def _plain_distribution(state):
+    """Unpickling of a ShardedPanelDistribution: the host-list PanelDistribution it was materialised to."""
+    d = PanelDistribution.__new__(PanelDistribution)
+    d.__setstate__(state)
+    return d
+
+
+class ShardedPanelDistribution(PanelDistribution):
+    """The PanelDistribution of a sharded run (distributed.legacy_panel_distribution_distributed): ``S``,
+    ``distinct``, ``spectrum``, ``sum_squares``, ``max_multiplicity`` and the estimators are the WHOLE job's,
+    on every rank (the owners' records summed in the call's all_reduce), under the constructor's consistency
+    check.  What a rank holds of the list itself:
+
+    ``owned()``: this rank's owner list, host ``(first, mult)`` ascending in first -- the panels whose
+    h1 % world is this rank, with the job's lowest draw index and the job's count of each.
+
+    ``candidates``: ``(first, mult)`` of every owner's ``top_keep`` most frequent entries (any order).
+    Multiplicity descending, then first index ascending, is a total order, so the job's ``top_keep``
+    most frequent panels are among them: ``top(m)`` for m <= ``top_keep`` is answered from them, their rows
+    re-drawn by index, one panel each, through ``redraw.draw(first, 1)`` -- no collective, any rank, alone.
+
+    ``multiplicities()``, ``count()``, ``top(m > top_keep)`` and pickling need the whole list: they re-draw
+    the job's panels [0, S) on this rank (``redraw()``, the distributed.PanelRedraw of the run's
+    found_panels) and count them (``panel_multiplicities_host``); from then on the object is a host-list
+    distribution, and pickles as a plain PanelDistribution.  A materialised list whose spectrum differs from
+    the reduced one raises RuntimeError.  ``redraw=None`` (the panels were not kept): the estimators and
+    ``owned()`` work, the others raise RuntimeError with PanelSet's message."""
+
+    def __init__(self, S, distinct, spectrum, sum_squares, owned_first, owned_mult, candidates=None, top_keep=0,
+                 redraw=None, n=0, agent_ids=None):
+        self.S, self.distinct = int(S), int(distinct)
+        self.spectrum = np.ascontiguousarray(spectrum, np.int64)
+        self.sum_squares = int(sum_squares)
+        self.max_multiplicity = len(self.spectrum) - 1
+        j = np.arange(len(self.spectrum), dtype=np.int64)
+        if int(self.spectrum.sum()) != self.distinct or int((self.spectrum * j).sum()) != self.S:
+            raise ValueError("multiplicities of %d panels summing to %d do not describe %d draws of %d distinct panels"
+                             % (int(self.spectrum.sum()), int((self.spectrum * j).sum()), self.S, self.distinct))
+        self._owned = (owned_first, owned_mult)
+        cf, cm = candidates if candidates is not None else ((), ())
+        cf, cm = np.asarray(cf, np.int64).reshape(-1), np.asarray(cm, np.int64).reshape(-1)
+        order = np.lexsort((cf, -cm))
+        self.top_keep = max(0, int(top_keep))
+        self._cand = (cf[order][:self.top_keep], cm[order][:self.top_keep])
+        self._cand_rows = {}
+        self._whole = False                         # the whole list is on this rank (materialised)
+        self._first = self._mult = self._panels = None
+        self._sorted, self._rows = False, False
+        self.bind(redraw, n, agent_ids)
+
+    def bind(self, redraw, n, agent_ids):
+        """The run's PanelRedraw (None: panels not kept) and the encoding's agents, to decode rows with."""
+        self._redraw = redraw
+        self._n, self._ids = int(n), agent_ids
+        self._W = max((self._n + 63) // 64, 1)
+        return self
+
+    def owned(self):
+        """Host ``(first int64[u], mult int64[u])`` ascending in first: this rank's owner list."""
+        f, m = (self._host(a) for a in self._owned)
+        order = np.argsort(f, kind="stable")
+        return f[order], m[order]
+
+    def _materialise(self):
+        if self._whole:
+            return
+        if self._redraw is None:
+            raise RuntimeError(self._where)
+        panels = np.ascontiguousarray(self._redraw(), np.uint64).reshape(self.S, -1)
+        first, mult = panel_multiplicities_host(panels)
+        spectrum = np.bincount(mult, minlength=1) if len(mult) else np.zeros(1, np.int64)
+        if len(first) != self.distinct or not np.array_equal(spectrum, self.spectrum):
+            raise RuntimeError("panel multiplicities: the re-drawn panels hold %d distinct panels with another "
+                               "spectrum than the run reduced over %d" % (len(first), self.distinct))
+        self._first, self._mult, self._sorted = first, mult, True
+        self._panels, self._rows = panels[first], True
+        self._whole = True
+
+    def multiplicities(self):
+        self._materialise()
+        return super().multiplicities()
+
+    def count(self, panel):
+        self._materialise()
+        return super().count(panel)
+
+    def top(self, m):
+        m = max(0, min(int(m), self.distinct))
+        if self._whole or m > len(self._cand[0]):
+            self._materialise()
+            return super().top(m)
+        if self._redraw is None:
+            raise RuntimeError(self._where)
+        out = []
+        for f, c in zip(self._cand[0][:m].tolist(), self._cand[1][:m].tolist()):
+            if f not in self._cand_rows:
+                row = np.ascontiguousarray(self._redraw.draw(f, 1), np.uint64).reshape(-1)
+                self._cand_rows[f] = self._decode(row)
+            out.append((self._cand_rows[f], c))
+        return out
+
+    def __reduce__(self):
+        self._materialise()
+        return _plain_distribution, (PanelDistribution.__getstate__(self),)
+
+
 def unique_mult_device(d_hashes, d_panels, S, W, d_status, stream, n_bins=4096):
     """Enqueue csa_unique_mult_async + csa_mult_spectrum_async over a batch's device hashes and panels on
     ``stream`` (a torch stream); nothing waits.  Returns (first, mult, out): two int32 tensors of

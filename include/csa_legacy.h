@@ -417,6 +417,47 @@ int csa_unique_keys_async(const csa_instance *inst, int32_t k, uint64_t seed, ui
                           const uint64_t *d_seg_counts, void *d_scratch, uint64_t scratch_bytes,
                           uint64_t *d_unique, uint32_t *d_status, void *stream);
 
+/* The 32-byte exchange: the panel multiplicities of a sharded run.  The key of the 24-byte exchange
+ * with the rank's count of the panel as a fourth word, (h1, h2, panel_begin + first, multiplicity),
+ * merged -- not counted -- by the owner.
+ *
+ * Send side: the list csa_unique_mult_async wrote over this rank's d_hashes (n_panels entries):
+ * d_first / d_mult, of which the first min(*d_distinct, n_panels) entries are read -- the length on
+ * the device, entries past it never.  Every listed panel becomes one key in d_send_keys
+ * uint64[world][capacity][4], bucketed by owner h1 % world; d_send_counts uint64[world] (zeroed by the
+ * call) = keys per segment, unused keys are left unwritten.  The list IS the local dedupe: the call
+ * runs none of its own and needs no scratch.  A segment that would exceed `capacity` raises
+ * CSA_E_UNSUPPORTED in d_status (required), never a short segment.  n_panels == 0 writes zero counts
+ * and launches nothing else.  world <= 1024; panel_begin + n_panels <= 2^32 (CSA_E_UNSUPPORTED
+ * above: the merged list's indices are uint32).  CSA_E_INVALID, before any device call, for world or
+ * capacity == 0, a NULL d_send_keys / d_send_counts / d_status / d_distinct, or any other NULL
+ * pointer with n_panels > 0.
+ *
+ * Owner side: over the valid keys of n_segments segments of `capacity` keys (segment s holds
+ * d_seg_counts[s], device uint64) one list entry per distinct panel: d_mult[e] = the sum of its keys'
+ * multiplicities, d_first[e] = the lowest of their global indices.  d_first / d_mult: n_segments *
+ * capacity uint32 each, entries past the list hold zero; *d_distinct (uint64) is WRITTEN with the
+ * list's length (not accumulated).  Equality is csa_unique_async's, equal 128-bit hash AND equal
+ * bitmask: every key whose hash matches an earlier key is re-drawn on inst together with that key's
+ * panel (draw over an index list, Philox (k, seed, max_attempts) as the original draws, not counted
+ * in the draw statistics); equal bitmasks merge, a key behind a 128-bit collision gets an entry of its
+ * own, such keys merged among themselves by bitmask.  The order of the list is unspecified; the set of
+ * (first, multiplicity) pairs is exact and deterministic.  A merged multiplicity or index beyond
+ * uint32 raises CSA_E_UNSUPPORTED in d_status (required); n_segments * capacity < 2^32
+ * (CSA_E_UNSUPPORTED above).  d_scratch: csa_merge_mult_keys_scratch_bytes(n_segments * capacity, W)
+ * bytes.  Stream-ordered, no host wait, nothing allocated.  CSA_E_INVALID, before any device call,
+ * for a NULL pointer, capacity == 0, n_segments == 0 or scratch_bytes below that size. */
+int csa_exchange_mult_keys_async(const uint64_t *d_hashes, uint64_t n_panels, const uint32_t *d_first,
+                                 const uint32_t *d_mult, const uint64_t *d_distinct, uint64_t panel_begin,
+                                 uint32_t world, uint64_t capacity, uint64_t *d_send_keys,
+                                 uint64_t *d_send_counts, uint32_t *d_status, void *stream);
+uint64_t csa_merge_mult_keys_scratch_bytes(uint64_t n_keys, int32_t W);
+int csa_merge_mult_keys_async(const csa_instance *inst, int32_t k, uint64_t seed, uint32_t max_attempts,
+                              const uint64_t *d_keys, uint32_t n_segments, uint64_t capacity,
+                              const uint64_t *d_seg_counts, void *d_scratch, uint64_t scratch_bytes,
+                              uint32_t *d_first, uint32_t *d_mult, uint64_t *d_distinct, uint32_t *d_status,
+                              void *stream);
+
 /* Multi-GPU pair exchange: pack the upper triangle incl. the diagonal of the
  * n*n int64 pair counts row-major into n(n+1)/2 int32 (every count must be
  * < 2^31), and unpack it back (overwriting the upper triangle). */
