@@ -106,6 +106,12 @@ SIGNATURES = {
     "csa_merge_mult_keys_scratch_bytes": (_U64, [_U64, _I32]),
     "csa_merge_mult_keys_async": (ctypes.c_int, [_P, _I32, _U64, _U32, _P, _U32, _U64, _P, _P, _U64, _P, _P, _P, _P,
                                                  _P]),
+    "csa_rows_sort_tile": (_I32, []),
+    "csa_rows_sort_scratch_bytes": (_U64, [_U64, _I32]),
+    "csa_rows_sort_unique_async": (ctypes.c_int, [_P, _U64, _I32, _U64, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "csa_rows_merge_scratch_bytes": (_U64, [_U64, _U64, _I32]),
+    "csa_rows_merge_unique_async": (ctypes.c_int, [_P, _P, _P, _P, _U64, _P, _P, _P, _P, _U64, _I32, _P, _U64, _P, _P,
+                                                   _P, _U64, _P, _P, _P]),
 }
 
 _lib = None

@@ -271,9 +271,10 @@ class PanelSet:
     """Set of distinct panels (found_panels, analysis.py:171,186), lazily materialised.
 
     ``len()`` is the device's exact distinct-panel count; iteration / membership
-    decode the packed bitmasks (host array, or a device tensor copied on first
-    use) into sorted agent-id tuples, as the reference's set holds them.  A
-    sharded run keeps no panels: they are re-drawn where first read (``_redraw``).
+    decode the packed bitmasks (host array, or a device tensor sorted on the
+    device, of which only the distinct rows are copied) into sorted agent-id
+    tuples, as the reference's set holds them.  A sharded run keeps no panels:
+    they are re-drawn where first read (``_redraw``).
     """
 
     def __init__(self, unique_count, packed=None, n=0, agent_ids=None):
@@ -292,18 +293,61 @@ class PanelSet:
     _redraw = None
 
     def _panels(self):
-        """The kept (or re-drawn) panels, device tensor or host array; None if none were kept."""
+        """The kept (or re-drawn) panels, device tensor or host array; None if none were kept.  A re-draw
+        that streams (distributed.PanelRedraw.table) leaves the distinct rows alone, already sorted and
+        checked against the run's count: the job's S x W words exist nowhere."""
         if self._packed is None and self._redraw is not None:
-            self._packed, self._redraw = self._redraw(), None
-            self._check_count = True
+            rd = self._redraw         # kept until the read has succeeded: a raised guard or count leaves it to retry
+            if getattr(rd, "streams", None) is not None and rd.streams():
+                self._packed, self._are_distinct = rd.table(self._count)[0], True
+            else:
+                self._packed, self._check_count = rd(), True
+            self._redraw = None
         return self._packed
 
+    def _device_distinct(self, p):
+        """Sorted distinct rows of a device tensor of packed panels, as an int64[D, W] tensor on its device
+        (csa_rows_sort_unique_async; one host wait, for the length).  The sorted length is a second exact
+        count, independent of the hash-based one: it must equal len(self)."""
+        import torch
+        from .stats import rows_sort_unique_device
+        if self._dev_rows is None:
+            W = max((self._n + 63) // 64, 1)
+            with torch.cuda.device(p.device):
+                t = rows_sort_unique_device(p, p.numel() // W, W, torch.cuda.current_stream(p.device), lists=False)
+                d = int(t.length.item())
+            if d != self._count:
+                raise RuntimeError("found_panels: the sorted panels hold %d distinct panels, the run counted %d"
+                                   % (d, self._count))
+            # a view keeps all S rows of the output alive: with duplicates only the D rows are kept
+            self._dev_rows = t.rows if d == t.cap else t.rows[:d].clone()
+        return self._dev_rows
+
+    _dev_rows = None
+    _are_distinct = False       # _packed holds distinct sorted host rows already
+
+    def device_rows(self):
+        """The distinct panels, sorted as ``rows()`` sorts them, as an int64[D, W] tensor on the device the
+        kept panels are on; None when they are not on a device (not kept, host arrays, a sharded run)."""
+        from .stats import _is_device_tensor
+        if self._dev_rows is None and _is_device_tensor(self._packed):
+            self._device_distinct(self._packed)
+        return self._dev_rows
+
     def _distinct(self, p):
-        """Sorted distinct rows of packed panels p; a re-drawn set must have the run's exact count."""
-        if hasattr(p, "device") and not isinstance(p, np.ndarray):
-            p = p.cpu().numpy()
+        """Sorted distinct rows of packed panels p; a re-drawn set must have the run's exact count.  Panels on
+        a device are sorted there and only the distinct rows copied (CSA_ROWS_HOST=1: all of them, and
+        np.unique on the host)."""
+        from .stats import rows_host_path
         W = max((self._n + 63) // 64, 1)
+        if hasattr(p, "device") and not isinstance(p, np.ndarray):
+            if p.is_cuda and not rows_host_path():
+                d = self._device_distinct(p)
+                return np.ascontiguousarray(d.cpu().numpy()).view(np.uint64).reshape(-1, W)
+            p = p.cpu().numpy()
         p = np.ascontiguousarray(p).view(np.uint64).reshape(-1, W)
+        if self._are_distinct:
+            return p
         rows = np.unique(p, axis=0) if len(p) else p
         if getattr(self, "_check_count", False) and len(rows) != self._count:
             raise RuntimeError("found_panels: the re-drawn panels hold %d distinct panels, the run counted %d"
@@ -331,7 +375,8 @@ class PanelSet:
 
     def rows(self):
         """The distinct panels as a host uint64[u, W] array (sorted rows), or None when the panels
-        were not kept.  Device panels are copied to the host here; a sharded run's are re-drawn."""
+        were not kept.  Of device panels the distinct rows are copied to the host here; a sharded run's
+        are re-drawn (and deduplicated on the device as they are, where the re-draw streams)."""
         W = (self._n + 63) // 64
         if self._panels() is None:
             if self._set is None:
@@ -344,7 +389,7 @@ class PanelSet:
                     rows[i, q >> 6] |= np.uint64(1) << np.uint64(q & 63)
             return np.unique(rows, axis=0) if len(rows) else rows
         self._packed = self._distinct(self._packed)   # keep the host rows (a re-draw happens once)
-        self._check_count = False
+        self._check_count, self._are_distinct = False, True
         return self._packed
 
     # pickling (run_legacy_or_retrieve dumps the returned tuple, analysis.py:284-290): only host

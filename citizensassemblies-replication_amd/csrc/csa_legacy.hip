@@ -3717,3 +3717,108 @@ int csa_merge_mult_keys_async(const csa_instance *I, int32_t k, uint64_t seed, u
 }
 
 }  // extern "C"
+
+// The sorted distinct-row table (distinct_rows.inc) stands after the 32-byte exchange, for the same reason.
+namespace {
+#include "distinct_rows.inc"
+
+// [p, p + bytes) and [q, q + qbytes) share a byte
+inline bool rs_overlap(const void *p, uint64_t bytes, const void *q, uint64_t qbytes) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && bytes && qbytes && a < b + qbytes && b < a + bytes;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t csa_rows_sort_tile(void) { return kRsTile; }
+
+uint64_t csa_rows_sort_scratch_bytes(uint64_t n_rows, int32_t W) {
+    (void)W;   // records are (word 0, index): the scratch does not grow with the row length
+    return rs_layout(n_rows).bytes;
+}
+
+int csa_rows_sort_unique_async(const uint64_t *d_rows, uint64_t n_rows, int32_t W, uint64_t index_base,
+                               void *d_scratch, uint64_t scratch_bytes, uint64_t *d_out_rows, uint32_t *d_first,
+                               uint32_t *d_mult, uint64_t *d_distinct, uint32_t *d_status, void *stream) {
+    if (W < 1 || !d_distinct) return fail(CSA_E_INVALID, "rows sort: bad arguments");
+    if (n_rows && (!d_rows || !d_scratch || !d_out_rows))
+        return fail(CSA_E_INVALID, "rows sort: NULL pointer with %llu rows", (unsigned long long)n_rows);
+    if (n_rows >= (1ull << 32) || index_base > (1ull << 32) - n_rows)
+        return fail(CSA_E_UNSUPPORTED, "rows sort: index_base + n_rows > 2^32, or 2^32 rows (u32 indices)");
+    const RsLayout Y = rs_layout(n_rows);
+    if (n_rows && (scratch_bytes < Y.bytes || ((uintptr_t)d_scratch & 7)))
+        return fail(CSA_E_INVALID, "rows sort: scratch_bytes < csa_rows_sort_scratch_bytes, or scratch not 8-byte aligned");
+    if (rs_overlap(d_out_rows, n_rows * W * 8, d_rows, n_rows * W * 8))
+        return fail(CSA_E_INVALID, "rows sort: d_out_rows aliases d_rows");
+    const hipStream_t st = (hipStream_t)stream;
+    if (n_rows == 0) {
+        HIPCHK(hipMemsetAsync(d_distinct, 0, 8, st));
+        return CSA_OK;
+    }
+    char *scratch = static_cast<char *>(d_scratch);
+    auto keys = [&](int b) { return reinterpret_cast<uint64_t *>(scratch + Y.keys[b]); };
+    auto idx = [&](int b) { return reinterpret_cast<uint32_t *>(scratch + Y.idx[b]); };
+    RsSrc src = {d_rows, nullptr, nullptr, nullptr, nullptr, nullptr, kRsSentinel, W, index_base, 0};
+    RsLen len = {n_rows, nullptr, nullptr, 0, 0};
+    const unsigned nb = (unsigned)Y.n_blocks;
+    hipLaunchKernelGGL(rs_tile_sort_kernel<>, dim3(nb), dim3(kRsThreads), 0, st, src, n_rows, keys(0), idx(0));
+    int buf = 0;
+    for (uint64_t L = kRsTile; L < n_rows; L *= 2, buf ^= 1)   // at most 22 passes
+        hipLaunchKernelGGL(rs_merge_kernel<>, dim3(nb), dim3(kRsThreads), 0, st, src, len, L,
+                           (const uint64_t *)keys(buf), (const uint32_t *)idx(buf), keys(buf ^ 1), idx(buf ^ 1));
+    rs_compact(src, len, n_rows, Y, scratch, buf, n_rows, d_out_rows, d_first, d_mult, d_distinct, d_status, st);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+uint64_t csa_rows_merge_scratch_bytes(uint64_t cap_a, uint64_t cap_b, int32_t W) {
+    (void)W;
+    return rs_layout(cap_a + cap_b).bytes;
+}
+
+int csa_rows_merge_unique_async(const uint64_t *d_a_rows, const uint32_t *d_a_first, const uint32_t *d_a_mult,
+                                const uint64_t *d_a_len, uint64_t cap_a, const uint64_t *d_b_rows,
+                                const uint32_t *d_b_first, const uint32_t *d_b_mult, const uint64_t *d_b_len,
+                                uint64_t cap_b, int32_t W, void *d_scratch, uint64_t scratch_bytes,
+                                uint64_t *d_out_rows, uint32_t *d_out_first, uint32_t *d_out_mult, uint64_t cap_out,
+                                uint64_t *d_out_len, uint32_t *d_status, void *stream) {
+    if (W < 1 || !d_a_len || !d_b_len || !d_out_len || !d_status)
+        return fail(CSA_E_INVALID, "rows merge: bad arguments");
+    if (d_out_len == d_a_len || d_out_len == d_b_len)   // the input lengths are read after the output's is written
+        return fail(CSA_E_INVALID, "rows merge: d_out_len aliases an input length");
+    if ((cap_a && (!d_a_rows || !d_a_first || !d_a_mult)) || (cap_b && (!d_b_rows || !d_b_first || !d_b_mult)))
+        return fail(CSA_E_INVALID, "rows merge: NULL list with a non-zero capacity");
+    const uint64_t cap_n = cap_a + cap_b;
+    if (cap_n && cap_out && (!d_out_rows || !d_out_first || !d_out_mult))
+        return fail(CSA_E_INVALID, "rows merge: NULL output with a non-zero capacity");
+    if (cap_n && !d_scratch) return fail(CSA_E_INVALID, "rows merge: NULL scratch");
+    if (cap_a >= (1ull << 32) || cap_b >= (1ull << 32) || cap_n >= (1ull << 32) - 1)
+        return fail(CSA_E_UNSUPPORTED, "rows merge: cap_a + cap_b >= 2^32 - 1 (u32 indices)");
+    const RsLayout Y = rs_layout(cap_n);
+    if (cap_n && (scratch_bytes < Y.bytes || ((uintptr_t)d_scratch & 7)))
+        return fail(CSA_E_INVALID, "rows merge: scratch_bytes < csa_rows_merge_scratch_bytes, or scratch not 8-byte aligned");
+    const uint64_t out_bytes = std::min(cap_out, cap_n) * W * 8;
+    if (rs_overlap(d_out_rows, out_bytes, d_a_rows, cap_a * W * 8) || rs_overlap(d_out_rows, out_bytes, d_b_rows, cap_b * W * 8))
+        return fail(CSA_E_INVALID, "rows merge: d_out_rows aliases an input");
+    const hipStream_t st = (hipStream_t)stream;
+    if (cap_n == 0) {
+        HIPCHK(hipMemsetAsync(d_out_len, 0, 8, st));
+        return CSA_OK;
+    }
+    char *scratch = static_cast<char *>(d_scratch);
+    auto keys = [&](int b) { return reinterpret_cast<uint64_t *>(scratch + Y.keys[b]); };
+    auto idx = [&](int b) { return reinterpret_cast<uint32_t *>(scratch + Y.idx[b]); };
+    RsSrc src = {d_a_rows, d_b_rows, d_a_first, d_b_first, d_a_mult, d_b_mult, (uint32_t)cap_a, W, 0, 1};
+    RsLen len = {0, reinterpret_cast<const unsigned long long *>(d_a_len),
+                 reinterpret_cast<const unsigned long long *>(d_b_len), cap_a, cap_b};
+    hipLaunchKernelGGL(rs_records_kernel<>, dim3((unsigned)((cap_n + 255) / 256)), dim3(256), 0, st, src, len, keys(0),
+                       idx(0));
+    hipLaunchKernelGGL(rs_merge_kernel<>, dim3((unsigned)Y.n_blocks), dim3(kRsThreads), 0, st, src, len, (uint64_t)0,
+                       (const uint64_t *)keys(0), (const uint32_t *)idx(0), keys(1), idx(1));
+    rs_compact(src, len, cap_n, Y, scratch, 1, cap_out, d_out_rows, d_out_first, d_out_mult, d_out_len, d_status, st);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+}  // extern "C"

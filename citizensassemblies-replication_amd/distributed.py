@@ -556,8 +556,10 @@ class PanelRedraw:
     panels [0, S) of the whole job -- every rank's shard -- can be drawn again on any one process.
     Calling this re-draws them in chunks of ``chunk`` panels through ``draw(begin, count)`` (a
     callable returning uint64[count, W]; ``device_redraw`` for the product path) into one host
-    array, with no collective: any rank may iterate, test membership or pickle its found_panels at
-    any time, alone.  The reference only ever takes len() of the set (analysis.py:575, 580) and
+    array -- or, where the draw offers device chunks (``streams``), ``table`` folds them on the device
+    into the sorted table of distinct panels, bounded by the distinct count and not by S -- with no
+    collective: any rank may iterate, test membership or pickle its found_panels at any time, alone.
+    The reference only ever takes len() of the set (analysis.py:575, 580) and
     pickles it (analysis.py:290); len() needs no re-draw (the exchange's exact count)."""
 
     def __init__(self, draw, S, W, chunk=1 << 20):
@@ -570,12 +572,56 @@ class PanelRedraw:
             out[off:off + c] = self.draw(off, c)
         return out
 
+    def streams(self):
+        """The draw offers device chunks (``device_chunk`` / ``tables``, as ``device_redraw``'s does) and
+        CSA_ROWS_HOST=1 does not force the host path: ``table`` is the way to read the panels."""
+        from .stats import rows_host_path
+        return hasattr(self.draw, "device_chunk") and hasattr(self.draw, "tables") and not rows_host_path()
+
+    def table(self, count, lists=False):
+        """The streaming form: the job's distinct panels as host ``(rows uint64[D, W] sorted as
+        PanelSet.rows() sorts them, first int64[D], mult int64[D])`` -- the lists None unless ``lists`` --
+        without the S x W array.  Per chunk: re-draw it on the device, sort-unique it with its global
+        indices (csa_rows_sort_unique_async), merge it into the table so far (csa_rows_merge_unique_async),
+        whose capacity is ``count``, the run's exact distinct count, in ping-pong buffers; nothing is read
+        in between.  Then one host wait: status, length, the D rows and lists.  A length other than
+        ``count`` -- or a table that overflowed, i.e. more distinct panels than counted -- raises
+        RuntimeError; so does, before anything is drawn, a job whose buffers exceed the free device memory
+        (stats.table_bytes)."""
+        from . import _native as N
+        from .stats import table_bytes
+        count, W = int(count), max(self.W, 1)
+        C = max(1, min(self.chunk, self.S))
+        ops = self.draw.tables()
+        need, free = table_bytes(count, C, W), ops.free_bytes()
+        if need > free:
+            raise RuntimeError("found_panels: reading %d distinct panels of %d draws needs %d bytes of device memory, "
+                               "%d are free" % (count, self.S, need, free))
+        acc, spare = ops.new_table(count, W), ops.new_table(count, W)
+        for off in range(0, self.S, self.chunk):
+            c = min(self.chunk, self.S - off)
+            part = ops.sort_unique(self.draw.device_chunk(off, c), c, W, off)
+            acc, spare = ops.merge(acc, part, spare), acc
+        words, length, rows, first, mult = ops.read(acc, lists, getattr(self.draw, "status", None))
+        N.raise_status(words[:4])                       # the re-draw's own status block
+        if words[4] == N.CSA_E_UNSUPPORTED:
+            raise RuntimeError("found_panels: the re-drawn panels hold more than %d distinct panels, the run "
+                               "counted %d" % (count, count))
+        N.raise_status(words[4:])
+        if length != count:
+            raise RuntimeError("found_panels: the re-drawn panels hold %d distinct panels, the run counted %d"
+                               % (length, count))
+        return rows, first, mult
+
 
 def device_redraw(enc, k, seed, device, max_attempts=0):
     """``draw(begin, count)`` for PanelRedraw on ``device``: csa_redraw_async (the batch draw's kernel
     and Philox counters, not counted in the instance's draw statistics) into a device buffer, then one
-    copy to the host.  The re-drawn status block is decoded: the original call already succeeded on
-    every rank, so an error here is raised, never ignored."""
+    copy to the host.  The callable also carries ``device_chunk(begin, count)``, the same chunk left on the
+    device with no copy and no status read, ``status``, the one block all such chunks raise into, and
+    ``tables()``, the sorted-table operations PanelRedraw.table streams them through.  The re-drawn
+    status block is decoded: the original call already succeeded on every rank, so an error here is
+    raised, never ignored."""
     import torch
     from . import _native as N
     W = enc.W
@@ -593,6 +639,28 @@ def device_redraw(enc, k, seed, device, max_attempts=0):
         N.raise_status(words)
         return host.numpy().view(np.uint64).reshape(count, W)
 
+    def device_chunk(begin, count):
+        """The chunk as a device tensor (int64 words, count * W), enqueued on the device's current stream:
+        no host copy, no status read -- every chunk of a re-draw raises into ``draw.status``."""
+        with torch.cuda.device(device):
+            st = torch.cuda.current_stream(device)
+            if draw.status is None:
+                draw.status = torch.zeros(4, dtype=torch.int32, device=device)
+            buf = torch.empty(max(count * W, 1), dtype=torch.int64, device=device)
+            N.check(N.lib().csa_redraw_async(enc.handle, int(k), seed64, int(begin), int(count), int(max_attempts),
+                                             N.ptr(buf), N.ptr(draw.status), ctypes.c_void_p(st.cuda_stream)))
+        return buf
+
+    def tables():
+        """The table operations of a streamed read (stats.DeviceRowTables) on the same device and stream; a
+        fresh status block for the re-draw it serves."""
+        from .stats import DeviceRowTables
+        with torch.cuda.device(device):
+            draw.status = torch.zeros(4, dtype=torch.int32, device=device)
+            return DeviceRowTables(device, torch.cuda.current_stream(device))
+
+    draw.status = None
+    draw.device_chunk, draw.tables = device_chunk, tables
     return draw
 
 
@@ -646,8 +714,9 @@ def legacy_probabilities_distributed(instance, iterations, random_seed, keep_pan
     found_panels: len() is the exchange's exact global count.  With more than one rank (or a forced
     exchange) nothing else is kept and nothing is sent: iterating, ``in``, ``rows()`` or pickling on
     ANY rank re-draws the job's panels [0, S) on that rank's GPU (PanelRedraw, csa_redraw_async) and
-    deduplicates them there -- no collective, so a rank may do it alone, at any time.  One rank (no
-    exchange): the panels of the call are the whole run's and stay on the device, decoded when read, as
+    deduplicates them there, chunk by chunk into the sorted table of distinct panels (PanelRedraw.table:
+    the read is bounded by the distinct count, not by S) -- no collective, so a rank may do it alone, at
+    any time.  One rank (no exchange): the panels of the call are the whole run's and stay on the device, decoded when read, as
     the one-GPU call does.  ``keep_panels=False``: len() only.  The draw statistics
     (analysis.LAST_RUN_STATS) are summed over ranks.  ``timings`` (a dict) gets the host-side stage
     times in ms.  ``groups`` (a stats.GroupSet; analysis.legacy_composition's sharded form): every rank

@@ -740,7 +740,9 @@ class ShardedPanelDistribution(PanelDistribution):
 
     ``multiplicities()``, ``count()``, ``top(m > top_keep)`` and pickling need the whole list: they re-draw
     the job's panels [0, S) on this rank (``redraw()``, the distributed.PanelRedraw of the run's
-    found_panels) and count them (``panel_multiplicities_host``); from then on the object is a host-list
+    found_panels) and count them -- on the device where the re-draw streams (``PanelRedraw.table``: the sorted
+    table of distinct rows with first index and count, D entries copied and ordered by first index here), on
+    the host otherwise (``panel_multiplicities_host``); from then on the object is a host-list
     distribution, and pickles as a plain PanelDistribution.  A materialised list whose spectrum differs from
     the reduced one raises RuntimeError.  ``redraw=None`` (the panels were not kept): the estimators and
     ``owned()`` work, the others raise RuntimeError with PanelSet's message."""
@@ -785,14 +787,22 @@ class ShardedPanelDistribution(PanelDistribution):
             return
         if self._redraw is None:
             raise RuntimeError(self._where)
-        panels = np.ascontiguousarray(self._redraw(), np.uint64).reshape(self.S, -1)
-        first, mult = panel_multiplicities_host(panels)
+        if getattr(self._redraw, "streams", None) is not None and self._redraw.streams():
+            # the sorted table, folded on the device chunk by chunk: D entries reach the host, ordered by
+            # first index here
+            rows, first, mult = self._redraw.table(self.distinct, lists=True)
+            order = np.argsort(first, kind="stable")
+            first, mult, kept = first[order], mult[order], rows[order]
+        else:
+            panels = np.ascontiguousarray(self._redraw(), np.uint64).reshape(self.S, -1)
+            first, mult = panel_multiplicities_host(panels)
+            kept = panels[first]
         spectrum = np.bincount(mult, minlength=1) if len(mult) else np.zeros(1, np.int64)
         if len(first) != self.distinct or not np.array_equal(spectrum, self.spectrum):
             raise RuntimeError("panel multiplicities: the re-drawn panels hold %d distinct panels with another "
                                "spectrum than the run reduced over %d" % (len(first), self.distinct))
         self._first, self._mult, self._sorted = first, mult, True
-        self._panels, self._rows = panels[first], True
+        self._panels, self._rows = kept, True
         self._whole = True
 
     def multiplicities(self):
@@ -844,6 +854,195 @@ def unique_mult_device(d_hashes, d_panels, S, W, d_status, stream, n_bins=4096):
                                     N.ptr(mult), N.ptr(out), N.ptr(d_status), sp))
     N.check(L.csa_mult_spectrum_async(N.ptr(mult), N.ptr(out), S, N.ptr(out[1:]), n_bins, N.ptr(out[1 + n_bins:]), sp))
     return first, mult, out
+
+
+# --- the distinct panels as a sorted table (csrc/distinct_rows.inc) ---------------------------------------
+# found_panels read on the device: the distinct rows in PanelSet.rows()'s order (np.unique(axis=0): word 0
+# most significant, unsigned), each with its lowest draw index and its count.  csa_rows_sort_unique_async
+# makes the table of one chunk, csa_rows_merge_unique_async folds it into the table so far, so neither the
+# host nor the device ever holds a sharded job's S x W words.  The ``*_host`` functions are the two
+# contracts in numpy (the checkers); HostRowTables / DeviceRowTables put either pair behind the one
+# interface distributed.PanelRedraw.table streams through.
+
+def rows_host_path():
+    """CSA_ROWS_HOST=1: read found_panels through the host np.unique path everywhere (A/B runs)."""
+    import os
+    return os.environ.get("CSA_ROWS_HOST") == "1"
+
+
+def rows_sort_unique_host(rows, index_base=0):
+    """``(rows uint64[D, W], first int64[D], mult int64[D])`` of packed rows uint64[n, W]: the distinct rows
+    ascending (word 0 most significant, unsigned), per row ``index_base`` + the lowest input index holding it
+    and the number of inputs holding it -- csa_rows_sort_unique_async's contract."""
+    p = np.ascontiguousarray(rows, np.uint64)
+    if p.ndim != 2:
+        raise ValueError("rows must be uint64[n, W]")
+    if len(p) == 0:
+        return p.copy(), np.zeros(0, np.int64), np.zeros(0, np.int64)
+    u, first, mult = np.unique(p, axis=0, return_index=True, return_counts=True)
+    return u, first.astype(np.int64) + int(index_base), mult.astype(np.int64)
+
+
+def rows_merge_unique_host(a, b):
+    """The sorted distinct union of two ``(rows, first, mult)`` tables, each sorted and distinct: a row in
+    both gets the lower ``first`` and the summed ``mult`` -- csa_rows_merge_unique_async's contract."""
+    ra, rb = (np.ascontiguousarray(t[0], np.uint64) for t in (a, b))
+    if not len(ra) or not len(rb):
+        r, f, m = b if not len(ra) else a
+        return np.ascontiguousarray(r, np.uint64).copy(), np.asarray(f, np.int64).copy(), np.asarray(m, np.int64).copy()
+    u, inv = np.unique(np.concatenate([ra, rb]), axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    first = np.full(len(u), np.iinfo(np.int64).max, np.int64)
+    mult = np.zeros(len(u), np.int64)
+    np.minimum.at(first, inv, np.concatenate([np.asarray(a[1], np.int64), np.asarray(b[1], np.int64)]))
+    np.add.at(mult, inv, np.concatenate([np.asarray(a[2], np.int64), np.asarray(b[2], np.int64)]))
+    return u, first, mult
+
+
+class RowTable:
+    """A sorted distinct-row table of capacity ``cap`` rows: ``rows`` [cap, W], ``first`` / ``mult`` [cap]
+    (uint32 words), ``length`` one uint64 word beside them (device tensors, or numpy arrays on the host)."""
+
+    def __init__(self, rows, first, mult, length, cap, W):
+        self.rows, self.first, self.mult, self.length, self.cap, self.W = rows, first, mult, length, int(cap), int(W)
+
+
+def table_bytes(cap, chunk, W):
+    """Device bytes of a streamed re-draw: the table of ``cap`` rows and its ping-pong twin, one chunk (its
+    panels and its sorted table) and the larger of the two scratches."""
+    L = N.lib()
+    cap, chunk, W = max(int(cap), 1), max(int(chunk), 1), max(int(W), 1)
+    one = lambda rows: rows * (8 * W + 8)
+    return 2 * one(cap) + 8 * chunk * W + one(chunk) + \
+        max(int(L.csa_rows_sort_scratch_bytes(chunk, W)), int(L.csa_rows_merge_scratch_bytes(cap, chunk, W)))
+
+
+class HostRowTables:
+    """The table operations on numpy arrays through the host mirrors: what DeviceRowTables does on a GPU, for
+    draws that hand out host chunks behind the device interface (tests; the C oracle standing in for a GPU).
+    ``free_bytes``: what the size guard is told is free."""
+
+    def __init__(self, free_bytes=1 << 62):
+        self._free = int(free_bytes)
+        self.status = np.zeros(4, np.uint32)
+
+    def free_bytes(self):
+        return self._free
+
+    def new_table(self, cap, W):
+        cap, W = max(int(cap), 1), max(int(W), 1)
+        return RowTable(np.zeros((cap, W), np.uint64), np.zeros(cap, np.int64), np.zeros(cap, np.int64),
+                        np.zeros(1, np.uint64), cap, W)
+
+    def sort_unique(self, rows, n, W, index_base):
+        r, f, m = rows_sort_unique_host(np.asarray(rows).view(np.uint64).reshape(-1, max(W, 1))[:n], index_base)
+        return RowTable(r, f, m, np.array([len(r)], np.uint64), max(n, 1), W)
+
+    def merge(self, a, b, out):
+        la, lb = (min(int(t.length[0]), t.cap) for t in (a, b))
+        r, f, m = rows_merge_unique_host((a.rows[:la], a.first[:la], a.mult[:la]),
+                                         (b.rows[:lb], b.first[:lb], b.mult[:lb]))
+        if len(r) > out.cap and not self.status[0]:
+            self.status[:] = (N.CSA_E_UNSUPPORTED, 0xFFFFFFFF, 0xFFFFFFFF, 0)
+        keep = min(len(r), out.cap)
+        out.rows[:keep], out.first[:keep], out.mult[:keep], out.length[0] = r[:keep], f[:keep], m[:keep], len(r)
+        return out
+
+    def read(self, table, lists, draw_status=None):
+        d = min(int(table.length[0]), table.cap)
+        words = np.concatenate([np.zeros(4, np.uint32) if draw_status is None else np.asarray(draw_status, np.uint32),
+                                self.status])
+        return (words, int(table.length[0]), table.rows[:d].copy(),
+                table.first[:d].copy() if lists else None, table.mult[:d].copy() if lists else None)
+
+
+def rows_sort_unique_device(d_rows, n_rows, W, stream, index_base=0, lists=True):
+    """Enqueue csa_rows_sort_unique_async over ``n_rows`` device rows (int64 words, row-major) on ``stream`` (a
+    torch stream); nothing waits.  Returns a RowTable of capacity max(n_rows, 1) on the rows' device (``first``
+    / ``mult`` None without ``lists``).  The scratch comes from torch's allocator on that stream, which reuses
+    it only for work ordered after this on the same stream."""
+    import torch
+    L = N.lib()
+    n, W = int(n_rows), int(W)
+    dev = d_rows.device
+    cap = max(n, 1)
+    with torch.cuda.stream(stream):
+        need = int(L.csa_rows_sort_scratch_bytes(n, W))
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        rows = torch.empty((cap, W), dtype=torch.int64, device=dev)
+        first = torch.empty(cap, dtype=torch.int32, device=dev) if lists else None
+        mult = torch.empty(cap, dtype=torch.int32, device=dev) if lists else None
+        length = torch.empty(1, dtype=torch.int64, device=dev)
+    N.check(L.csa_rows_sort_unique_async(N.ptr(d_rows), n, W, int(index_base), N.ptr(scratch), need, N.ptr(rows),
+                                         N.ptr(first), N.ptr(mult), N.ptr(length), None,
+                                         ctypes.c_void_p(stream.cuda_stream)))
+    return RowTable(rows, first, mult, length, cap, W)
+
+
+def rows_merge_unique_device(a, b, out, d_status, stream):
+    """Enqueue csa_rows_merge_unique_async of RowTables ``a`` and ``b`` into ``out`` (all on one device, lengths
+    read there) on ``stream``; nothing waits.  A union beyond ``out.cap`` raises CSA_E_UNSUPPORTED in
+    ``d_status`` (int32[4] on the device).  Scratch as in rows_sort_unique_device.  Returns ``out``."""
+    import torch
+    L = N.lib()
+    W = a.W
+    with torch.cuda.stream(stream):
+        need = int(L.csa_rows_merge_scratch_bytes(a.cap, b.cap, W))
+        scratch = torch.empty(need, dtype=torch.uint8, device=out.rows.device)
+    N.check(L.csa_rows_merge_unique_async(N.ptr(a.rows), N.ptr(a.first), N.ptr(a.mult), N.ptr(a.length), a.cap,
+                                          N.ptr(b.rows), N.ptr(b.first), N.ptr(b.mult), N.ptr(b.length), b.cap, W,
+                                          N.ptr(scratch), need, N.ptr(out.rows), N.ptr(out.first), N.ptr(out.mult),
+                                          out.cap, N.ptr(out.length), N.ptr(d_status),
+                                          ctypes.c_void_p(stream.cuda_stream)))
+    return out
+
+
+class DeviceRowTables:
+    """The table operations on ``device``, enqueued on ``stream``: csa_rows_sort_unique_async and
+    csa_rows_merge_unique_async, with one status block for every merge of a re-draw."""
+
+    def __init__(self, device, stream):
+        import torch
+        self.device, self.stream = device, stream
+        with torch.cuda.stream(stream):
+            self.status = torch.zeros(4, dtype=torch.int32, device=device)
+
+    def free_bytes(self):
+        """The device's free memory (torch.cuda.mem_get_info).  Blocks torch's caching allocator holds but has
+        not handed out are not in it, though the table's tensors could reuse them: right after a large call
+        the guard errs on the side of refusing (torch.cuda.empty_cache() returns them to the figure)."""
+        import torch
+        return int(torch.cuda.mem_get_info(self.device)[0])
+
+    def new_table(self, cap, W):
+        import torch
+        cap, W = max(int(cap), 1), max(int(W), 1)
+        with torch.cuda.stream(self.stream):
+            return RowTable(torch.empty((cap, W), dtype=torch.int64, device=self.device),
+                            torch.empty(cap, dtype=torch.int32, device=self.device),
+                            torch.empty(cap, dtype=torch.int32, device=self.device),
+                            torch.zeros(1, dtype=torch.int64, device=self.device), cap, W)
+
+    def sort_unique(self, rows, n, W, index_base):
+        return rows_sort_unique_device(rows, n, W, self.stream, index_base)
+
+    def merge(self, a, b, out):
+        return rows_merge_unique_device(a, b, out, self.status, self.stream)
+
+    def read(self, table, lists, draw_status=None):
+        """The one host wait: [draw status | table status | length], then the D rows (and lists)."""
+        import torch
+        with torch.cuda.stream(self.stream):
+            ds = draw_status if draw_status is not None else torch.zeros_like(self.status)
+            head = torch.cat([ds.view(torch.int64), self.status.view(torch.int64), table.length]).cpu().numpy()
+            words, length = head[:4].view(np.uint32).copy(), int(head[4])
+            d = min(length, table.cap)
+            rows = np.ascontiguousarray(table.rows[:d].cpu().numpy()).view(np.uint64).reshape(d, table.W)
+            first = mult = None
+            if lists:
+                first = table.first[:d].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+                mult = table.mult[:d].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        return words, length, rows, first, mult
 
 
 def composition_difference(a, b):

@@ -458,6 +458,51 @@ int csa_merge_mult_keys_async(const csa_instance *inst, int32_t k, uint64_t seed
                               uint32_t *d_first, uint32_t *d_mult, uint64_t *d_distinct, uint32_t *d_status,
                               void *stream);
 
+/* The distinct panels as a sorted table (reading the reference's `found_panels` set, analysis.py:171,
+ * 186, and what it pickles, analysis.py:290, without a host copy of all S panels).  Rows are W uint64
+ * words, row-major (the panels' own layout); their order is lexicographic with word 0 most significant,
+ * every word compared unsigned -- np.unique(axis=0)'s order, PanelSet.rows()'s.  Both operations are
+ * stream-ordered, read lengths on the device, wait for nothing and allocate nothing.
+ *
+ * Sort-unique of a chunk: d_out_rows (n_rows * W words) receives the distinct rows of d_rows ascending;
+ * per output row d_first (or NULL) = index_base + the lowest input index holding it, d_mult (or NULL) =
+ * the number of input rows holding it (n_rows uint32 each); *d_distinct (uint64) is WRITTEN with the
+ * list's length.  Output entries past the length are unspecified; nothing outside the stated sizes is
+ * written and d_rows is not modified.  An LDS sort of csa_rows_sort_tile() records (word 0, index) per
+ * workgroup, merge passes over pairs of runs partitioned by merge path, then flag / scan / gather.
+ * d_scratch: csa_rows_sort_scratch_bytes(n_rows, W) bytes, 8-byte aligned.  n_rows == 0 writes
+ * *d_distinct = 0 and launches nothing else.  d_status is not used by the sort (may be NULL).
+ * CSA_E_UNSUPPORTED for index_base + n_rows > 2^32 (d_first is uint32, as in the merged multiplicity
+ * lists) and for n_rows == 2^32.  CSA_E_INVALID, before any device call, for W < 1, a NULL d_distinct,
+ * a NULL d_rows / d_scratch / d_out_rows with n_rows > 0, scratch_bytes below the stated size, or
+ * d_out_rows overlapping d_rows.
+ *
+ * Merge-unique of two such lists: A and B, each sorted and distinct with its first and mult, lengths
+ * min(*d_a_len, cap_a) and min(*d_b_len, cap_b) read on the device -- entries past a length are never
+ * read.  The output is the sorted distinct union; a row present in both gets first = min(first_A,
+ * first_B) and mult = mult_A + mult_B.  *d_out_len (uint64) is WRITTEN with the union's size.  A union
+ * larger than cap_out sets CSA_E_UNSUPPORTED in d_status (required) and writes nothing past cap_out
+ * rows (*d_out_len still holds the union's size); so does a merged mult beyond uint32.  The sort's
+ * merge-path pass and compaction, over one pair of runs.  d_scratch:
+ * csa_rows_merge_scratch_bytes(cap_a, cap_b, W) bytes, 8-byte aligned.  cap_a + cap_b == 0 writes
+ * *d_out_len = 0 and launches nothing else.  CSA_E_UNSUPPORTED for cap_a + cap_b >= 2^32 - 1.
+ * CSA_E_INVALID, before any device call, for W < 1, a NULL length pointer or d_status, a NULL list
+ * pointer with a non-zero capacity, a NULL output or scratch with work to do, scratch_bytes below the
+ * stated size, d_out_rows overlapping an input list, or d_out_len being one of the input lengths. */
+int32_t csa_rows_sort_tile(void);
+uint64_t csa_rows_sort_scratch_bytes(uint64_t n_rows, int32_t W);
+int csa_rows_sort_unique_async(const uint64_t *d_rows, uint64_t n_rows, int32_t W, uint64_t index_base,
+                               void *d_scratch, uint64_t scratch_bytes, uint64_t *d_out_rows,
+                               uint32_t *d_first /* or NULL */, uint32_t *d_mult /* or NULL */,
+                               uint64_t *d_distinct, uint32_t *d_status, void *stream);
+uint64_t csa_rows_merge_scratch_bytes(uint64_t cap_a, uint64_t cap_b, int32_t W);
+int csa_rows_merge_unique_async(const uint64_t *d_a_rows, const uint32_t *d_a_first, const uint32_t *d_a_mult,
+                                const uint64_t *d_a_len, uint64_t cap_a, const uint64_t *d_b_rows,
+                                const uint32_t *d_b_first, const uint32_t *d_b_mult, const uint64_t *d_b_len,
+                                uint64_t cap_b, int32_t W, void *d_scratch, uint64_t scratch_bytes,
+                                uint64_t *d_out_rows, uint32_t *d_out_first, uint32_t *d_out_mult,
+                                uint64_t cap_out, uint64_t *d_out_len, uint32_t *d_status, void *stream);
+
 /* Multi-GPU pair exchange: pack the upper triangle incl. the diagonal of the
  * n*n int64 pair counts row-major into n(n+1)/2 int32 (every count must be
  * < 2^31), and unpack it back (overwriting the upper triangle). */
