@@ -32,6 +32,11 @@ from uq_mult_kernel / unique_mult_kernel and mult_spectrum_kernel on the device:
 spectrum, sample coverage, the Chao1 bound on the panels possible, the most frequent panels);
 panel_multiplicities_host is the same list in numpy
 
+plus two such tables side by side (csa_rows_join_async / csa_rows_find_async over the sorted distinct
+rows): PanelSet's set operators and comparisons, legacy_panel_comparison(instance, iterations) -- two
+seeds and their PanelComparison (shared panels, held-out coverage, overlap, cross-sample collision) --
+and legacy_portfolio_overlap, a run beside a LEXIMIN / XMIN portfolio (PortfolioOverlap)
+
 plus xmin._get_panel_not_in_portfolio_if_possible (XMIN's LEGACY caller,
 xmin.py:464-474) on the device.
 """
@@ -46,6 +51,9 @@ from .stats import (CompositionHistogram, GroupSet, agent_groups, feature_groups
 from .stats import (WeightedCompositionHistogram, composition_difference, group_whist_host,  # noqa: F401
                     portfolio_group_composition)
 from .stats import PanelDistribution, panel_multiplicities_host  # noqa: F401
+from .analysis import legacy_panel_comparison, legacy_portfolio_overlap  # noqa: F401
+from .stats import (PanelComparison, PortfolioOverlap, compare_panel_distributions, portfolio_overlap,  # noqa: F401
+                    rows_find_host, rows_join_host)
 from . import _native, xmin  # noqa: F401
 
 __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_cats",
@@ -55,4 +63,6 @@ __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_c
            "feature_groups", "group_composition", "intersection_groups", "intersectional_representation",
            "leximin_composition", "xmin_composition", "portfolio_composition", "WeightedCompositionHistogram",
            "composition_difference", "group_whist_host", "portfolio_group_composition",
-           "legacy_panel_distribution", "PanelDistribution", "panel_multiplicities_host"]
+           "legacy_panel_distribution", "PanelDistribution", "panel_multiplicities_host",
+           "legacy_panel_comparison", "legacy_portfolio_overlap", "PanelComparison", "PortfolioOverlap",
+           "compare_panel_distributions", "portfolio_overlap", "rows_join_host", "rows_find_host"]

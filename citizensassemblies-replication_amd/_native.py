@@ -112,6 +112,10 @@ SIGNATURES = {
     "csa_rows_merge_scratch_bytes": (_U64, [_U64, _U64, _I32]),
     "csa_rows_merge_unique_async": (ctypes.c_int, [_P, _P, _P, _P, _U64, _P, _P, _P, _P, _U64, _I32, _P, _U64, _P, _P,
                                                    _P, _U64, _P, _P, _P]),
+    "csa_rows_join_scratch_bytes": (_U64, [_U64, _U64, _I32]),
+    "csa_rows_join_async": (ctypes.c_int, [_P, _P, _P, _U64, _P, _P, _P, _U64, _I32, _U32, _U64, _U64, _P, _U64, _P,
+                                           _P, _P, _U64, _P, _P, _P, _P]),
+    "csa_rows_find_async": (ctypes.c_int, [_P, _P, _U64, _I32, _P, _U64, _P, _P]),
 }
 
 _lib = None

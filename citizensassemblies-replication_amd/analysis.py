@@ -28,6 +28,10 @@ Kept names and semantics (reference file:line):
   * ``legacy_panel_distribution``      new: ``legacy_probabilities`` with a fourth result, how often each
                                        distinct panel was drawn (stats.PanelDistribution) from uq_mult_kernel /
                                        unique_mult_kernel and mult_spectrum_kernel beside the distinct count.
+  * ``legacy_panel_comparison``,       new: two runs (seeds 0 and 1, analysis.py:536-541) or a run and a portfolio
+    ``legacy_portfolio_overlap``       side by side at the level of whole panels (stats.PanelComparison,
+                                       stats.PortfolioOverlap), and ``PanelSet``'s set operators, from
+                                       csa_rows_join_async / csa_rows_find_async over the sorted distinct rows.
 The LEXIMIN / XMIN solvers (Gurobi) and the plotting code stay in the reference (CPU).
 """
 import ctypes
@@ -391,6 +395,131 @@ class PanelSet:
         self._packed = self._distinct(self._packed)   # keep the host rows (a re-draw happens once)
         self._check_count, self._are_distinct = False, True
         return self._packed
+
+    # --- set algebra (the reference's found_panels is a Python set, printed beside LEXIMIN's and XMIN's,
+    # analysis.py:575-582).  Two PanelSets of one instance whose distinct rows are on one device: one
+    # csa_rows_join_async, the result's rows staying there.  Anything else -- host rows, unpickled sets,
+    # different devices, a plain set / frozenset / iterable of agent-id tuples -- goes through the host mirror
+    # (stats.rows_join_host) over rows().  Never through Python tuples.
+
+    def _kept(self):
+        if self._panels() is None and self._set is None:
+            raise RuntimeError(self._where)
+
+    def _pack_all(self, panels):
+        """Agent-id tuples -> uint64[len, W] rows in the given order, as stats._pack_ids packs one; KeyError for
+        an id that is no agent."""
+        pos = {aid: q for q, aid in enumerate(self._ids)}
+        panels = list(panels)
+        rows = np.zeros((len(panels), max((self._n + 63) // 64, 1)), np.uint64)
+        for i, panel in enumerate(panels):
+            for aid in panel:
+                q = pos[aid]
+                rows[i, q >> 6] |= np.uint64(1) << np.uint64(q & 63)
+        return rows
+
+    def _pack(self, panels):
+        """Agent-id tuples -> sorted distinct rows."""
+        rows = self._pack_all(panels)
+        return np.unique(rows, axis=0) if len(rows) else rows
+
+    def _from_rows(self, rows, count, on_device):
+        out = PanelSet(count, rows, self._n, self._ids)
+        out._are_distinct = True
+        if on_device:
+            out._dev_rows = rows
+        return out
+
+    def _join(self, other, select, swap=False):
+        """(record, result): the join's 11 integers and, with ``select``, the selected rows as a PanelSet.
+        ``swap``: ``other`` is the left operand (the reflected operators)."""
+        from . import stats as St
+        self._kept()
+        if isinstance(other, PanelSet):
+            St._same_instance(self, other)
+            other._kept()
+            a, b = (other, self) if swap else (self, other)
+            da, db = a.device_rows(), b.device_rows()
+            if da is not None and db is not None and da.device == db.device and not St.rows_host_path():
+                return self._join_device(da, db, select)
+            ra, rb = a.rows(), b.rows()
+        else:
+            ra, rb = self.rows(), self._pack(other)
+            if swap:
+                ra, rb = rb, ra
+        rows, _, _, count, record = St.rows_join_host((ra, None), (rb, None), select)
+        return record, (self._from_rows(rows, count, False) if select else None)
+
+    def _join_device(self, da, db, select):
+        import torch
+        from . import stats as St
+        dev, W = da.device, max((self._n + 63) // 64, 1)
+        with torch.cuda.device(dev):
+            T = St.DeviceRowTables(dev, torch.cuda.current_stream(dev))
+            ta, tb = (St.RowTable(d, None, None, torch.full((1,), d.shape[0], dtype=torch.int64, device=dev),
+                                  d.shape[0], W) for d in (da, db))
+            j = T.join(ta, tb, select, mults=False)
+            head = torch.cat([T.status.view(torch.int64), j.length, j.record]).cpu().numpy()   # the one host wait
+        N.raise_status(head[:2].view(np.uint32))
+        record, count = [int(x) for x in head[3:].view(np.uint64)], int(head[2])
+        if not select:
+            return record, None
+        rows = j.rows if count == j.cap else j.rows[:count].clone()     # a view would keep the whole output alive
+        return record, self._from_rows(rows, count, True)
+
+    def intersection(self, other):
+        return self._join(other, 4)[1]
+
+    def union(self, other):
+        return self._join(other, 7)[1]
+
+    def difference(self, other):
+        return self._join(other, 1)[1]
+
+    def symmetric_difference(self, other):
+        return self._join(other, 3)[1]
+
+    __and__, __or__, __sub__, __xor__ = intersection, union, difference, symmetric_difference
+    __rand__, __ror__, __rxor__ = intersection, union, symmetric_difference
+
+    def __rsub__(self, other):
+        return self._join(other, 1, swap=True)[1]
+
+    def isdisjoint(self, other):
+        return self._join(other, 0)[0][1] == 0
+
+    def issubset(self, other):
+        return self._join(other, 0)[0][2] == 0
+
+    def issuperset(self, other):
+        return self._join(other, 0)[0][3] == 0
+
+    __le__, __ge__ = issubset, issuperset
+
+    def __lt__(self, other):
+        record = self._join(other, 0)[0]
+        return record[2] == 0 and record[3] > 0
+
+    def __gt__(self, other):
+        record = self._join(other, 0)[0]
+        return record[3] == 0 and record[2] > 0
+
+    def contains_many(self, panels):
+        """bool[len(panels)]: which of the panels (agent-id tuples, any order, repeats allowed) are in the set
+        -- one csa_rows_find_async over the sorted rows where they are on a device, its mirror otherwise."""
+        from . import stats as St
+        self._kept()
+        W = max((self._n + 63) // 64, 1)
+        q = self._pack_all(panels)
+        d = self.device_rows()
+        if d is None or St.rows_host_path() or not len(q):
+            return St.rows_find_host(self.rows(), q) != St.FIND_MISSING
+        import torch
+        with torch.cuda.device(d.device):
+            t = St.RowTable(d, None, None, torch.full((1,), d.shape[0], dtype=torch.int64, device=d.device), d.shape[0], W)
+            at = St.rows_find_device(t, torch.from_numpy(q.view(np.int64)).to(d.device), len(q),
+                                     torch.cuda.current_stream(d.device))
+            return at.cpu().numpy().view(np.uint32) != St.FIND_MISSING
 
     # pickling (run_legacy_or_retrieve dumps the returned tuple, analysis.py:284-290): only host
     # data -- the distinct panels as packed rows (or the materialised set) -- so the pickle loads
@@ -800,6 +929,47 @@ def legacy_panel_distribution(instance: Instance, iterations: int, random_seed: 
                                   "call distributed.legacy_panel_distribution_distributed" % D.world_size())
     run = _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, None, multiplicity=True)
     return run.alloc, run.panels, run.histogram, run.distribution
+
+
+def legacy_panel_comparison(instance: Instance, iterations: int, seed_a: int = 0, seed_b: int = 1, *, rng: str = None):
+    """Two LEGACY runs of ``iterations`` draws each and their panel tables side by side: returns
+    ``(run_a, run_b, comparison)``.
+
+    This is the reference's two-sample design (analyze_instance draws LEGACY with seeds 0 and 1 and reads the
+    first sample's minimiser in the second, analysis.py:536-541) carried to whole panels: an estimate made on
+    one run is checked on the other.  Each ``run_x`` is what ``legacy_panel_distribution(instance,
+    iterations, seed_x, rng=rng)`` returns, bit for bit.  ``comparison`` is the ``stats.PanelComparison`` of the
+    two distributions (``stats.compare_panel_distributions``: both runs' kept panels sorted on the device, one
+    csa_rows_join_async, 15 words copied): ``mass_b_on_a()`` is the held-out coverage ``run_a``'s Good-Turing
+    ``coverage()`` predicts, ``cross_collision()`` the independent estimate beside ``collision_probability()``.
+    With torch.distributed initialised and world size > 1 this call raises NotImplementedError, as
+    ``legacy_panel_distribution`` does."""
+    from . import distributed as D
+    from .stats import compare_panel_distributions
+    if D.world_size() > 1:
+        raise NotImplementedError("legacy_panel_comparison: sharded runs (world size %d) are not supported here; "
+                                  "call distributed.legacy_panel_distribution_distributed" % D.world_size())
+    run_a = legacy_panel_distribution(instance, iterations, seed_a, rng=rng)
+    run_b = legacy_panel_distribution(instance, iterations, seed_b, rng=rng)
+    return run_a, run_b, compare_panel_distributions(run_a[3], run_b[3])
+
+
+def legacy_portfolio_overlap(instance: Instance, distribution, portfolio, probabilities):
+    """A LEGACY run's ``stats.PanelDistribution`` beside a LEXIMIN / XMIN ``(portfolio, probabilities)``: how
+    much of LEGACY's mass lies on the portfolio's panels and how much of the portfolio's on panels LEGACY ever
+    drew -- a ``stats.PortfolioOverlap`` (``stats.portfolio_overlap``: one csa_rows_find_async of the packed
+    portfolio in the run's sorted table).  The portfolio is packed as ``portfolio_probabilities`` packs it:
+    paired with ``zip``, KeyError for an agent id that is not in the instance."""
+    from .stats import portfolio_overlap
+    enc = encode_cached(instance.categories, instance.agents)
+    pos = getattr(enc, "_pos", None)
+    if pos is None:
+        pos = enc._pos = {aid: p for p, aid in enumerate(enc.agent_ids)}
+    pairs = list(zip(portfolio, probabilities))
+    rows = _membership([panel for panel, _ in pairs], enc.n, pos.__getitem__)[1]
+    if distribution._n != enc.n or list(distribution._ids or ()) != list(enc.agent_ids):
+        raise ValueError("the distribution is over another instance (its agents differ)")
+    return portfolio_overlap(distribution, rows, np.array([pob for _, pob in pairs], np.float64).reshape(-1))
 
 
 def legacy_composition(instance: Instance, iterations: int, random_seed: int, groups, *, rng: str = None,

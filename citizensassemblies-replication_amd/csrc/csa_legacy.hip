@@ -3822,3 +3822,108 @@ int csa_rows_merge_unique_async(const uint64_t *d_a_rows, const uint32_t *d_a_fi
 }
 
 }  // extern "C"
+
+// The join and the lookup over such tables (rows_join.inc) stand after them, for the same reason.
+namespace {
+#include "rows_join.inc"
+}  // namespace
+
+extern "C" {
+
+uint64_t csa_rows_join_scratch_bytes(uint64_t cap_a, uint64_t cap_b, int32_t W) {
+    (void)W;
+    return rj_layout(cap_a + cap_b).bytes;
+}
+
+int csa_rows_join_async(const uint64_t *d_a_rows, const uint32_t *d_a_mult, const uint64_t *d_a_len, uint64_t cap_a,
+                        const uint64_t *d_b_rows, const uint32_t *d_b_mult, const uint64_t *d_b_len, uint64_t cap_b,
+                        int32_t W, uint32_t select, uint64_t scale_a, uint64_t scale_b, void *d_scratch,
+                        uint64_t scratch_bytes, uint64_t *d_out_rows, uint32_t *d_out_mult_a, uint32_t *d_out_mult_b,
+                        uint64_t cap_out, uint64_t *d_out_len, uint64_t *d_record, uint32_t *d_status, void *stream) {
+    if (W < 1 || !d_a_len || !d_b_len || !d_out_len || !d_record || !d_status)
+        return fail(CSA_E_INVALID, "rows join: bad arguments");
+    if (select > 7) return fail(CSA_E_INVALID, "rows join: select %u names a class beyond 1 | 2 | 4", select);
+    if (scale_a >= (1ull << 32) || scale_b >= (1ull << 32))
+        return fail(CSA_E_INVALID, "rows join: a scale of 2^32 or more (the products must fit 64 bits)");
+    // the input lengths are read after the output's length and the record are written
+    if (d_out_len == d_a_len || d_out_len == d_b_len || rs_overlap(d_record, 88, d_a_len, 8) ||
+        rs_overlap(d_record, 88, d_b_len, 8) || rs_overlap(d_record, 88, d_out_len, 8))
+        return fail(CSA_E_INVALID, "rows join: d_out_len or d_record aliases a length");
+    if ((cap_a && !d_a_rows) || (cap_b && !d_b_rows))
+        return fail(CSA_E_INVALID, "rows join: NULL rows with a non-zero capacity");
+    const uint64_t cap_n = cap_a + cap_b;
+    if (cap_n && !d_scratch) return fail(CSA_E_INVALID, "rows join: NULL scratch");
+    if (cap_a >= (1ull << 32) || cap_b >= (1ull << 32) || cap_n >= (1ull << 32) - 1)
+        return fail(CSA_E_UNSUPPORTED, "rows join: cap_a + cap_b >= 2^32 - 1 (u32 indices)");
+    const RjLayout J = rj_layout(cap_n);
+    if (cap_n && (scratch_bytes < J.bytes || ((uintptr_t)d_scratch & 7)))
+        return fail(CSA_E_INVALID, "rows join: scratch_bytes < csa_rows_join_scratch_bytes, or scratch not 8-byte aligned");
+    const uint64_t out_n = std::min(cap_out, cap_n);
+    if (rs_overlap(d_out_rows, out_n * W * 8, d_a_rows, cap_a * W * 8) ||
+        rs_overlap(d_out_rows, out_n * W * 8, d_b_rows, cap_b * W * 8))
+        return fail(CSA_E_INVALID, "rows join: d_out_rows aliases an input");
+    for (const uint32_t *out : {(const uint32_t *)d_out_mult_a, (const uint32_t *)d_out_mult_b})
+        if (rs_overlap(out, out_n * 4, d_a_mult, cap_a * 4) || rs_overlap(out, out_n * 4, d_b_mult, cap_b * 4))
+            return fail(CSA_E_INVALID, "rows join: an output multiplicity list aliases an input's");
+    const hipStream_t st = (hipStream_t)stream;
+    if (cap_n == 0) {
+        HIPCHK(hipMemsetAsync(d_out_len, 0, 8, st));
+        HIPCHK(hipMemsetAsync(d_record, 0, 88, st));
+        return CSA_OK;
+    }
+    const RsLayout &Y = J.rs;
+    char *scratch = static_cast<char *>(d_scratch);
+    auto keys = [&](int b) { return reinterpret_cast<uint64_t *>(scratch + Y.keys[b]); };
+    auto idx = [&](int b) { return reinterpret_cast<uint32_t *>(scratch + Y.idx[b]); };
+    uint32_t *pos = reinterpret_cast<uint32_t *>(scratch + Y.pos), *bc = reinterpret_cast<uint32_t *>(scratch + Y.bc);
+    uint8_t *cls = reinterpret_cast<uint8_t *>(scratch + Y.flags);
+    uint64_t *slab = reinterpret_cast<uint64_t *>(scratch + J.slab);
+    unsigned long long *out_len = reinterpret_cast<unsigned long long *>(d_out_len);
+    RsSrc src = {d_a_rows, d_b_rows, nullptr, nullptr, d_a_mult, d_b_mult, (uint32_t)cap_a, W, 0, 1};
+    RsLen len = {0, reinterpret_cast<const unsigned long long *>(d_a_len),
+                 reinterpret_cast<const unsigned long long *>(d_b_len), cap_a, cap_b};
+    const RjMult mu = {d_a_mult, d_b_mult, scale_a, scale_b};
+    const unsigned nb = (unsigned)Y.n_blocks;
+    hipLaunchKernelGGL(rs_records_kernel<>, dim3((unsigned)((cap_n + 255) / 256)), dim3(256), 0, st, src, len, keys(0),
+                       idx(0));
+    hipLaunchKernelGGL(rs_merge_kernel<>, dim3(nb), dim3(kRsThreads), 0, st, src, len, (uint64_t)0,
+                       (const uint64_t *)keys(0), (const uint32_t *)idx(0), keys(1), idx(1));
+    hipLaunchKernelGGL(rj_flag_kernel<>, dim3(nb), dim3(kRsThreads), 0, st, src, len, mu, select,
+                       (const uint64_t *)keys(1), (const uint32_t *)idx(1), cls, bc, slab);
+    hipLaunchKernelGGL(rs_scan_kernel<>, dim3(1), dim3(kRsThreads), 0, st, len, bc, Y.n_blocks, pos, cap_out, out_len,
+                       d_status);
+    hipLaunchKernelGGL(rj_summary_kernel<>, dim3(1), dim3(kRsThreads), 0, st, (const uint64_t *)slab, Y.n_blocks,
+                       reinterpret_cast<unsigned long long *>(d_record), d_status);
+    if (select && out_n && (d_out_rows || d_out_mult_a || d_out_mult_b)) {
+        hipLaunchKernelGGL(rj_pos_kernel<>, dim3(nb), dim3(kRsThreads), 0, st, len, select, (const uint8_t *)cls,
+                           (const uint32_t *)bc, pos);
+        const uint64_t words = out_n * (uint64_t)W;
+        const unsigned grid = (unsigned)std::min<uint64_t>((words + 255) / 256, 1u << 20);
+        hipLaunchKernelGGL(rj_gather_kernel<>, dim3(grid), dim3(256), 0, st, src, mu, (const uint32_t *)idx(1),
+                           (const uint8_t *)cls, (const uint32_t *)pos, (const unsigned long long *)out_len, cap_out,
+                           d_out_rows, d_out_mult_a, d_out_mult_b);
+    }
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+int csa_rows_find_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W,
+                        const uint64_t *d_queries, uint64_t n_queries, uint32_t *d_out_index, void *stream) {
+    if (W < 1 || !d_len) return fail(CSA_E_INVALID, "rows find: bad arguments");
+    if (cap && !d_rows) return fail(CSA_E_INVALID, "rows find: NULL rows with a non-zero capacity");
+    if (n_queries && (!d_queries || !d_out_index))
+        return fail(CSA_E_INVALID, "rows find: NULL pointer with %llu queries", (unsigned long long)n_queries);
+    if (cap >= (1ull << 32) - 1) return fail(CSA_E_UNSUPPORTED, "rows find: cap >= 2^32 - 1 (u32 indices)");
+    if (n_queries >= (1ull << 40)) return fail(CSA_E_UNSUPPORTED, "rows find: 2^40 queries or more");
+    if (rs_overlap(d_out_index, n_queries * 4, d_rows, cap * W * 8) ||
+        rs_overlap(d_out_index, n_queries * 4, d_queries, n_queries * W * 8) || rs_overlap(d_out_index, n_queries * 4, d_len, 8))
+        return fail(CSA_E_INVALID, "rows find: d_out_index aliases an input");
+    if (n_queries == 0) return CSA_OK;
+    hipLaunchKernelGGL(rj_find_kernel<>, dim3((unsigned)((n_queries + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       d_rows, reinterpret_cast<const unsigned long long *>(d_len), cap, W, d_queries, n_queries,
+                       d_out_index);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+}  // extern "C"

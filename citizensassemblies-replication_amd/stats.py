@@ -688,6 +688,8 @@ class PanelDistribution:
         if self._panels is None:
             raise RuntimeError(self._where)
         row = _pack_ids(panel, self._ids, self._W)
+        if self._table is not None and _is_device_tensor(self._table.rows):
+            return int(_table_counts(self._table, row.reshape(1, -1))[0])     # log D row compares, one word copied
         f, mult = self._sort()
         if _is_device_tensor(self._panels) and not self._rows:
             import torch
@@ -700,6 +702,43 @@ class PanelDistribution:
         if len(hit) == 0:
             return 0
         return int(mult[int(hit[0])].item()) if _is_device_tensor(mult) else int(mult[hit[0]])
+
+    _table = None
+
+    def table(self):
+        """The run as a sorted table: a RowTable of the D distinct panels ascending (``PanelSet.rows()``'s
+        order) with ``first`` and ``mult``, what ``compare_panel_distributions`` and ``portfolio_overlap``
+        join and search.  Kept panels on a device are sorted there (csa_rows_sort_unique_async; one host
+        wait, for the length and the sum) and the table stays on that device; otherwise it is built on the
+        host from the kept or pickled rows.  Its length must equal ``distinct`` and its multiplicities must
+        sum to ``S``: RuntimeError otherwise.  Built once."""
+        if self._table is not None:
+            return self._table
+        if self._panels is None:
+            raise RuntimeError(self._where)
+        W = self._W
+        if _is_device_tensor(self._panels) and not self._rows and not rows_host_path():
+            import torch
+            dev = self._panels.device
+            with torch.cuda.device(dev):
+                t = rows_sort_unique_device(self._panels, self.S, W, torch.cuda.current_stream(dev), lists=True)
+                d = min(int(t.length.item()), t.cap)
+                s = int((t.mult[:d].to(torch.int64) & 0xFFFFFFFF).sum().item())
+                if d != t.cap:       # a view would keep the sort's S-row output alive
+                    t = RowTable(t.rows[:d].clone(), t.first[:d].clone(), t.mult[:d].clone(), t.length, d, W)
+        else:
+            f, m = self.multiplicities()
+            rows = np.ascontiguousarray(self._panel_rows(np.arange(self.distinct)), np.uint64).reshape(-1, W)
+            if len(rows):
+                rows, at = np.unique(rows, axis=0, return_index=True)
+                f, m = f[at], m[at]
+            d, s = len(rows), int(m.sum())
+            t = RowTable(rows, f, m, np.array([d], np.uint64), d, W)
+        if d != self.distinct or s != self.S:
+            raise RuntimeError("panel table: %d sorted rows whose multiplicities sum to %d, the run counted %d distinct "
+                               "panels in %d draws" % (d, s, self.distinct, self.S))
+        self._table = t
+        return t
 
     def __getstate__(self):
         f, m = self.multiplicities()
@@ -812,6 +851,10 @@ class ShardedPanelDistribution(PanelDistribution):
     def count(self, panel):
         self._materialise()
         return super().count(panel)
+
+    def table(self):
+        self._materialise()
+        return super().table()
 
     def top(self, m):
         m = max(0, min(int(m), self.distinct))
@@ -948,6 +991,20 @@ class HostRowTables:
         out.rows[:keep], out.first[:keep], out.mult[:keep], out.length[0] = r[:keep], f[:keep], m[:keep], len(r)
         return out
 
+    def join(self, a, b, select, scales=(1, 1), cap_out=None):
+        """rows_join_host over two tables' first ``length`` rows, as a RowJoin of numpy arrays; more selected rows
+        than the capacity, or a sum beyond 64 bits, sets CSA_E_UNSUPPORTED in ``status``."""
+        la, lb = (min(int(t.length[0]), t.cap) for t in (a, b))
+        side = lambda t, n: (t.rows[:n], None if t.mult is None else np.asarray(t.mult[:n], np.int64) & 0xFFFFFFFF)
+        r, ma, mb, length, record = rows_join_host(side(a, la), side(b, lb), select, scales)
+        cap = _join_cap(a, b, select) if cap_out is None else int(cap_out)
+        if (length > cap or record[10]) and not self.status[0]:
+            self.status[:] = (N.CSA_E_UNSUPPORTED, 0xFFFFFFFF, 0xFFFFFFFF, 0)
+        return RowJoin(r[:cap], ma[:cap], mb[:cap], np.array([length], np.uint64), record, cap)
+
+    def find(self, table, queries):
+        return rows_find_host(table.rows[:min(int(table.length[0]), table.cap)], queries)
+
     def read(self, table, lists, draw_status=None):
         d = min(int(table.length[0]), table.cap)
         words = np.concatenate([np.zeros(4, np.uint32) if draw_status is None else np.asarray(draw_status, np.uint32),
@@ -1029,6 +1086,12 @@ class DeviceRowTables:
     def merge(self, a, b, out):
         return rows_merge_unique_device(a, b, out, self.status, self.stream)
 
+    def join(self, a, b, select, scales=(1, 1), cap_out=None, rows=True, mults=True):
+        return rows_join_device(a, b, select, self.status, self.stream, scales, cap_out, rows, mults)
+
+    def find(self, table, d_queries, n_queries):
+        return rows_find_device(table, d_queries, n_queries, self.stream)
+
     def read(self, table, lists, draw_status=None):
         """The one host wait: [draw status | table status | length], then the D rows (and lists)."""
         import torch
@@ -1043,6 +1106,286 @@ class DeviceRowTables:
                 first = table.first[:d].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
                 mult = table.mult[:d].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
         return words, length, rows, first, mult
+
+
+# --- two tables side by side (csrc/rows_join.inc) -----------------------------------------------------------
+# The join of two sorted distinct-row tables and the lookup of a few rows in one: what the set algebra of
+# analysis.PanelSet, the two-run comparison and the portfolio overlap are made of.  ``rows_join_host`` and
+# ``rows_find_host`` are csa_rows_join_async's and csa_rows_find_async's contracts in numpy.
+
+JOIN_ONLY_A, JOIN_ONLY_B, JOIN_BOTH = 1, 2, 4
+JOIN_RECORD = ("union", "shared", "only_a", "only_b", "sum_a", "sum_b", "shared_a", "shared_b", "cross", "overlap",
+               "overflow")
+FIND_MISSING = 0xFFFFFFFF
+
+
+class RowJoin:
+    """What a join gives: the selected union rows ``rows`` [cap, W] ascending with ``mult_a`` / ``mult_b`` [cap]
+    (0 where the row is absent from that side; any of the three None when not asked for), their number
+    ``length`` (one word) and the 11-word ``record`` over the whole union (JOIN_RECORD).  Device tensors, or
+    numpy arrays on the host, where ``record`` is a list of Python integers."""
+
+    def __init__(self, rows, mult_a, mult_b, length, record, cap):
+        self.rows, self.mult_a, self.mult_b, self.length, self.record, self.cap = rows, mult_a, mult_b, length, record, cap
+
+
+def _join_side(t):
+    rows = np.ascontiguousarray(t[0], np.uint64)
+    if rows.ndim != 2:
+        raise ValueError("rows must be uint64[n, W]")
+    mult = np.ones(len(rows), np.int64) if t[1] is None else np.asarray(t[1], np.int64).reshape(-1)
+    if len(mult) != len(rows):
+        raise ValueError("one multiplicity per row")
+    return rows, mult
+
+
+def rows_join_host(a, b, select, scales=(1, 1)):
+    """csa_rows_join_async's contract: ``a`` and ``b`` are ``(rows uint64[n, W], mult or None)``, each sorted and
+    distinct (None: every multiplicity 1).  Returns ``(rows, mult_a, mult_b, length, record)``: the union rows
+    whose class (1 only in a, 2 only in b, 4 in both) is in the mask ``select``, ascending, their multiplicities
+    on either side (int64, 0 where absent), their number, and the record of the whole union as 11 Python
+    integers (JOIN_RECORD; words 8 and 9 modulo 2^64 with word 10 = 1 when either did not fit)."""
+    select, (sa, sb) = int(select), (int(s) for s in scales)
+    if not 0 <= select <= 7 or not (0 <= sa < 1 << 32 and 0 <= sb < 1 << 32):
+        raise ValueError("select is a mask of 1 | 2 | 4 and the scales are below 2^32")
+    (ra, ma), (rb, mb) = _join_side(a), _join_side(b)
+    W = ra.shape[1] if len(ra) or not len(rb) else rb.shape[1]
+    if len(ra) + len(rb) == 0:
+        return np.zeros((0, W), np.uint64), np.zeros(0, np.int64), np.zeros(0, np.int64), 0, [0] * 11
+    u, inv = np.unique(np.concatenate([ra.reshape(-1, W), rb.reshape(-1, W)]), axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    xa, xb = np.zeros(len(u), np.int64), np.zeros(len(u), np.int64)
+    in_a, in_b = np.zeros(len(u), np.bool_), np.zeros(len(u), np.bool_)
+    xa[inv[:len(ra)]], in_a[inv[:len(ra)]] = ma, True
+    xb[inv[len(ra):]], in_b[inv[len(ra):]] = mb, True
+    cls = np.where(in_a & in_b, JOIN_BOTH, np.where(in_a, JOIN_ONLY_A, JOIN_ONLY_B))
+    both = cls == JOIN_BOTH
+    pa, pb = xa[both].tolist(), xb[both].tolist()
+    cross = sum(x * y for x, y in zip(pa, pb))
+    overlap = sum(min(x * sb, y * sa) for x, y in zip(pa, pb))
+    record = [len(u), int(both.sum()), int((cls == JOIN_ONLY_A).sum()), int((cls == JOIN_ONLY_B).sum()),
+              sum(ma.tolist()), sum(mb.tolist()), sum(pa), sum(pb), cross & (2 ** 64 - 1), overlap & (2 ** 64 - 1),
+              int(cross >= 2 ** 64 or overlap >= 2 ** 64)]
+    keep = (cls & select) != 0
+    return u[keep], xa[keep], xb[keep], int(keep.sum()), record
+
+
+def rows_find_host(table_rows, queries):
+    """csa_rows_find_async's contract: int64[Q], per query row the index of the equal row of the sorted distinct
+    ``table_rows``, or FIND_MISSING.  The queries need be neither sorted nor distinct."""
+    t = np.ascontiguousarray(table_rows, np.uint64)
+    q = np.ascontiguousarray(queries, np.uint64)
+    if t.ndim != 2 or q.ndim != 2 or (len(t) and len(q) and t.shape[1] != q.shape[1]):
+        raise ValueError("table and queries must be uint64[n, W] of one W")
+    out = np.full(len(q), FIND_MISSING, np.int64)
+    if not len(t) or not len(q):
+        return out
+    u, inv = np.unique(np.concatenate([t, q]), axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    where = np.full(len(u), FIND_MISSING, np.int64)
+    where[inv[:len(t)]] = np.arange(len(t))
+    return where[inv[len(t):]]
+
+
+def _join_cap(a, b, select):
+    """The most rows a join of capacities ``a.cap`` and ``b.cap`` can select."""
+    most = (a.cap if select & JOIN_ONLY_A else 0) + (b.cap if select & JOIN_ONLY_B else 0) + \
+        (min(a.cap, b.cap) if select & JOIN_BOTH else 0)
+    return min(most, a.cap + b.cap)
+
+
+def rows_join_device(a, b, select, d_status, stream, scales=(1, 1), cap_out=None, rows=True, mults=True):
+    """Enqueue csa_rows_join_async of RowTables ``a`` and ``b`` (on one device, lengths read there; a ``mult``
+    of None counts every row once) on ``stream``; nothing waits.  Returns a RowJoin on that device: outputs of
+    ``cap_out`` rows (default: the most ``select`` can give; ``rows`` / ``mults`` False: not written), the length
+    and the record as int64 tensors.  More selected rows than ``cap_out``, or a sum beyond 64 bits, raises
+    CSA_E_UNSUPPORTED in ``d_status`` (int32[4] on the device).  Scratch as in rows_sort_unique_device."""
+    import torch
+    L = N.lib()
+    W, select = a.W, int(select)
+    dev = a.length.device
+    cap = _join_cap(a, b, select) if cap_out is None else int(cap_out)
+    with torch.cuda.stream(stream):
+        need = int(L.csa_rows_join_scratch_bytes(a.cap, b.cap, W))
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty((cap, W), dtype=torch.int64, device=dev) if rows and select else None
+        mult_a = torch.empty(cap, dtype=torch.int32, device=dev) if mults and select else None
+        mult_b = torch.empty(cap, dtype=torch.int32, device=dev) if mults and select else None
+        length = torch.empty(1, dtype=torch.int64, device=dev)
+        record = torch.empty(len(JOIN_RECORD), dtype=torch.int64, device=dev)
+    N.check(L.csa_rows_join_async(N.ptr(a.rows), N.ptr(a.mult), N.ptr(a.length), a.cap,
+                                  N.ptr(b.rows), N.ptr(b.mult), N.ptr(b.length), b.cap, W, select,
+                                  int(scales[0]), int(scales[1]), N.ptr(scratch), need, N.ptr(out), N.ptr(mult_a),
+                                  N.ptr(mult_b), cap, N.ptr(length), N.ptr(record), N.ptr(d_status),
+                                  ctypes.c_void_p(stream.cuda_stream)))
+    return RowJoin(out, mult_a, mult_b, length, record, cap)
+
+
+def rows_find_device(table, d_queries, n_queries, stream):
+    """Enqueue csa_rows_find_async of ``n_queries`` device rows (int64 words, row-major) in RowTable ``table`` on
+    ``stream``; nothing waits.  Returns an int32 tensor of n_queries uint32 words: the index, or FIND_MISSING."""
+    import torch
+    n = int(n_queries)
+    with torch.cuda.stream(stream):
+        out = torch.empty(max(n, 1), dtype=torch.int32, device=table.length.device)
+    N.check(N.lib().csa_rows_find_async(N.ptr(table.rows), N.ptr(table.length), table.cap, table.W, N.ptr(d_queries),
+                                        n, N.ptr(out), ctypes.c_void_p(stream.cuda_stream)))
+    return out[:n]
+
+
+def _table_counts(table, queries):
+    """Host int64[P]: how often each of the P query rows (uint64[P, W]) was drawn, 0 for a row the table does not
+    hold.  A device table: the queries go up, one lookup, one gather of the multiplicities there, P counts come
+    back.  A host table: the mirror."""
+    q = np.ascontiguousarray(queries, np.uint64).reshape(-1, table.W)
+    if not len(q):
+        return np.zeros(0, np.int64)
+    if _is_device_tensor(table.rows):
+        import torch
+        dev = table.rows.device
+        with torch.cuda.device(dev):
+            d_q = torch.from_numpy(q.view(np.int64)).to(dev)
+            at = rows_find_device(table, d_q, len(q), torch.cuda.current_stream(dev)).to(torch.int64) & 0xFFFFFFFF
+            hit = at != FIND_MISSING
+            mult = table.mult.to(torch.int64) & 0xFFFFFFFF
+            counts = torch.where(hit, mult[torch.where(hit, at, torch.zeros_like(at))], torch.zeros_like(at))
+            return counts.cpu().numpy()
+    d = min(int(table.length[0]), table.cap)
+    at = rows_find_host(table.rows[:d], q)
+    mult = np.concatenate([np.asarray(table.mult[:d], np.int64) & 0xFFFFFFFF, [0]])
+    return mult[np.where(at == FIND_MISSING, d, at)]
+
+
+class PanelComparison:
+    """Two runs' panel tables side by side: the integers of a join's record (JOIN_RECORD) and the two runs'
+    draws ``S_a`` / ``S_b``.  Every figure is one division of two exact integers, so the device's record and
+    the host mirror's give the same floats.  With S = 0 on either side every figure is 0.0.
+
+    ``shared``, ``only_a``, ``only_b``, ``union``: distinct panels drawn by both runs, by one alone, by either.
+    """
+
+    def __init__(self, record, S_a, S_b):
+        self.record = [int(x) for x in record]
+        self.S_a, self.S_b = int(S_a), int(S_b)
+        self.union, self.shared, self.only_a, self.only_b = self.record[:4]
+
+    def _over(self, num, den):
+        return num / den if self.S_a and self.S_b and den else 0.0
+
+    def jaccard(self):
+        """Shared distinct panels over the union's."""
+        return self._over(self.shared, self.union)
+
+    def mass_a_on_b(self):
+        """The share of run a's draws that fell on panels run b saw: the held-out coverage that b's Good-Turing
+        ``coverage()`` predicts."""
+        return self._over(self.record[6], self.S_a)
+
+    def mass_b_on_a(self):
+        return self._over(self.record[7], self.S_b)
+
+    def overlap(self):
+        """sum min(m_a / S_a, m_b / S_b) over the shared panels: 1 minus the total variation distance of the two
+        empirical distributions."""
+        return self._over(self.record[9], self.S_a * self.S_b)
+
+    def total_variation(self):
+        return 1 - self.overlap() if self.S_a and self.S_b else 0.0
+
+    def cross_collision(self):
+        """sum m_a m_b / (S_a S_b): the chance that a draw of a and a draw of b are one panel, an unbiased
+        estimate of the sum of squared panel probabilities from independent samples -- beside
+        ``collision_probability()``, the within-sample one."""
+        return self._over(self.record[8], self.S_a * self.S_b)
+
+    def __eq__(self, other):
+        return isinstance(other, PanelComparison) and (self.record, self.S_a, self.S_b) == \
+            (other.record, other.S_a, other.S_b)
+
+    def __repr__(self):
+        return "PanelComparison(shared=%d, only_a=%d, only_b=%d, S_a=%d, S_b=%d)" % (
+            self.shared, self.only_a, self.only_b, self.S_a, self.S_b)
+
+
+def _same_instance(a, b):
+    if a._n != b._n or not (a._ids is b._ids or list(a._ids or ()) == list(b._ids or ())):
+        raise ValueError("the two sides are over different instances (their agents differ)")
+
+
+def compare_panel_distributions(a, b):
+    """The PanelComparison of two PanelDistributions over one instance (two seeds of LEGACY: the reference's
+    two-sample design, analysis.py:536-541, at the level of whole panels).  Both tables on one device: one
+    csa_rows_join_async (select 0: the record alone) and one host copy of 15 words; otherwise the host mirror.
+    The record's multiplicity sums must be the runs' S: RuntimeError otherwise.  ValueError for distributions
+    over different instances; distributions that kept no panels raise PanelSet's message."""
+    _same_instance(a, b)
+    ta, tb = a.table(), b.table()
+    if _is_device_tensor(ta.rows) and _is_device_tensor(tb.rows) and ta.rows.device == tb.rows.device:
+        import torch
+        dev = ta.rows.device
+        with torch.cuda.device(dev):
+            T = DeviceRowTables(dev, torch.cuda.current_stream(dev))
+            j = T.join(ta, tb, 0, (a.S, b.S))
+            head = torch.cat([T.status.view(torch.int64), j.record]).cpu().numpy()
+        words = head[:2].view(np.uint32)
+        record = [int(x) for x in head[2:].view(np.uint64)]
+    else:
+        host = lambda t: RowTable(*(x.cpu().numpy() if _is_device_tensor(x) else x for x in (t.rows, t.first, t.mult,
+                                                                                          t.length)), t.cap, t.W)
+        T = HostRowTables()
+        j = T.join(host(ta), host(tb), 0, (a.S, b.S))
+        words, record = T.status, j.record
+    N.raise_status(words)
+    if record[4] != a.S or record[5] != b.S:
+        raise RuntimeError("panel comparison: the tables' multiplicities sum to %d and %d, the runs drew %d and %d"
+                           % (record[4], record[5], a.S, b.S))
+    return PanelComparison(record, a.S, b.S)
+
+
+class PortfolioOverlap:
+    """A LEGACY run beside a LEXIMIN / XMIN portfolio.  ``counts`` (int64[P]): how often the run drew each
+    portfolio entry.  ``panels`` / ``panels_seen``: the portfolio's distinct panels, and those of them the run
+    ever drew.  ``legacy_mass``: the share of the run's draws on the portfolio's panels.  ``portfolio_mass_seen``:
+    the portfolio's probability on panels the run drew.  ``overlap``: sum over the distinct portfolio panels of
+    min(m / S, w), w a panel's weights added up: 1 minus the total variation distance between the run's
+    empirical distribution and the portfolio's."""
+
+    def __init__(self, counts, panels, panels_seen, legacy_mass, portfolio_mass_seen, overlap, S):
+        self.counts, self.panels, self.panels_seen, self.S = counts, int(panels), int(panels_seen), int(S)
+        self.legacy_mass, self.portfolio_mass_seen, self.overlap = legacy_mass, portfolio_mass_seen, overlap
+
+
+def portfolio_overlap(distribution, portfolio_rows, weights):
+    """The PortfolioOverlap of a PanelDistribution and a portfolio given as packed rows uint64[P, W] with float64
+    ``weights``.  One lookup of the P rows in the run's table and one gather of the multiplicities (on the
+    device where the table is there; P counts are copied), then on the host in portfolio order, every float sum
+    from ``0.`` by one float64 add per entry, left to right (as ``group_whist_host`` orders its sums):
+    ``portfolio_mass_seen`` adds w_p over the entries with a non-zero count; an entry that repeats an earlier
+    panel adds its weight to that panel's; ``overlap`` then adds min(m / S, w) over the distinct panels in
+    the order of their first entry, and ``legacy_mass`` is the integer sum of their m over S.  S = 0: 0.0."""
+    t = distribution.table()
+    rows = np.ascontiguousarray(portfolio_rows, np.uint64).reshape(-1, t.W)
+    w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    if len(w) != len(rows):
+        raise ValueError("one weight per portfolio panel")
+    counts = _table_counts(t, rows)
+    S = distribution.S
+    slot, summed, mult = {}, [], []
+    mass_seen = 0.
+    for key, m, x in zip(map(bytes, rows), counts.tolist(), w.tolist()):
+        if m:
+            mass_seen += x
+        e = slot.setdefault(key, len(summed))
+        if e == len(summed):
+            summed.append(x)
+            mult.append(m)
+        else:
+            summed[e] += x
+    overlap = 0.
+    for m, x in zip(mult, summed):
+        overlap += min(m / S, x) if S else 0.
+    return PortfolioOverlap(counts, len(summed), sum(1 for m in mult if m), sum(mult) / S if S else 0.0, mass_seen,
+                            overlap, S)
 
 
 def composition_difference(a, b):

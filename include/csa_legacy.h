@@ -503,6 +503,55 @@ int csa_rows_merge_unique_async(const uint64_t *d_a_rows, const uint32_t *d_a_fi
                                 uint64_t *d_out_rows, uint32_t *d_out_first, uint32_t *d_out_mult,
                                 uint64_t cap_out, uint64_t *d_out_len, uint32_t *d_status, void *stream);
 
+/* Two such tables side by side (the reference draws LEGACY twice, seeds 0 and 1, and reads one sample's
+ * result in the other, analysis.py:536-541; it prints found_panels beside LEXIMIN's and XMIN's sets,
+ * analysis.py:575-582): the join of two tables and the lookup of a few rows in one.  Both are
+ * stream-ordered, read lengths on the device, wait for nothing and allocate nothing.
+ *
+ * Join: A and B in the merge's input form -- rows sorted and distinct, lengths min(*d_a_len, cap_a) and
+ * min(*d_b_len, cap_b) read on the device, entries past a length never read; d_a_mult / d_b_mult uint32
+ * per row, or NULL: every multiplicity of that table is 1.  Every row of the sorted distinct union has a
+ * class: 1 = only in A, 2 = only in B, 4 = in both.  The union rows whose class is in the mask `select`
+ * go, ascending, to d_out_rows (cap_out * W words), with d_out_mult_a / d_out_mult_b (cap_out uint32
+ * each) = the row's multiplicity on that side, 0 where it is absent; each of the three may be NULL, and
+ * all are ignored with select == 0.  *d_out_len (uint64) is WRITTEN with the number of selected rows; a
+ * number beyond cap_out sets CSA_E_UNSUPPORTED in d_status (required) and writes nothing past cap_out
+ * rows.  d_record (11 uint64, required) is WRITTEN with the summary of the whole union, whatever select:
+ *   [0] union size            [1] rows in both          [2] rows only in A      [3] rows only in B
+ *   [4] sum of mult_a over A  [5] sum of mult_b over B  [6] sum of mult_a over the rows in both
+ *   [7] sum of mult_b over the rows in both             [8] sum of mult_a * mult_b over the rows in both
+ *   [9] sum of min(mult_a * scale_b, mult_b * scale_a) over the rows in both
+ *   [10] 1 if a sum did not fit 64 bits (only [8] and [9] can fail to), else 0; 1 also sets
+ *        CSA_E_UNSUPPORTED in d_status, and [8] / [9] then hold the low 64 bits.
+ * With scale_a = sum of A's mults and scale_b = sum of B's, [9] / (scale_a * scale_b) is the overlap
+ * sum min(p_A, p_B) of the two empirical distributions and [8] / (scale_a * scale_b) the cross-sample
+ * estimate of the sum of squared probabilities.  Every sum is an exact integer, the same on every run:
+ * integer adds only, carried in 128 bits where 64 can overflow; no float arithmetic, no atomics.  The
+ * merge's record and merge-path passes over the one pair of runs, then the join's own flag / scan /
+ * summary / position / gather.  d_scratch: csa_rows_join_scratch_bytes(cap_a, cap_b, W) bytes, 8-byte
+ * aligned.  cap_a + cap_b == 0 writes *d_out_len = 0 and a zero record and launches nothing else.
+ * CSA_E_UNSUPPORTED for cap_a + cap_b >= 2^32 - 1.  CSA_E_INVALID, before any device call, for W < 1, a
+ * NULL length, d_out_len, d_record or d_status, NULL rows with a non-zero capacity, a NULL scratch with
+ * work to do, scratch_bytes below the stated size, select > 7, a scale >= 2^32, an output overlapping an
+ * input list, or d_out_len / d_record overlapping a length.
+ *
+ * Lookup: d_out_index[q] (uint32) = the index of the row of the table (d_rows, min(*d_len, cap) rows)
+ * equal to query row q of d_queries (n_queries * W words), or 0xFFFFFFFF.  Queries need be neither
+ * sorted nor distinct; one binary search of at most 33 halvings each; no scratch.  n_queries == 0
+ * launches nothing.  CSA_E_UNSUPPORTED for cap >= 2^32 - 1.  CSA_E_INVALID, before any device call, for
+ * W < 1, a NULL d_len, NULL rows with a non-zero capacity, NULL queries or output with n_queries > 0,
+ * or d_out_index overlapping an input. */
+uint64_t csa_rows_join_scratch_bytes(uint64_t cap_a, uint64_t cap_b, int32_t W);
+int csa_rows_join_async(const uint64_t *d_a_rows, const uint32_t *d_a_mult /* or NULL */, const uint64_t *d_a_len,
+                        uint64_t cap_a, const uint64_t *d_b_rows, const uint32_t *d_b_mult /* or NULL */,
+                        const uint64_t *d_b_len, uint64_t cap_b, int32_t W, uint32_t select, uint64_t scale_a,
+                        uint64_t scale_b, void *d_scratch, uint64_t scratch_bytes,
+                        uint64_t *d_out_rows /* or NULL */, uint32_t *d_out_mult_a /* or NULL */,
+                        uint32_t *d_out_mult_b /* or NULL */, uint64_t cap_out, uint64_t *d_out_len,
+                        uint64_t *d_record, uint32_t *d_status, void *stream);
+int csa_rows_find_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W,
+                        const uint64_t *d_queries, uint64_t n_queries, uint32_t *d_out_index, void *stream);
+
 /* Multi-GPU pair exchange: pack the upper triangle incl. the diagonal of the
  * n*n int64 pair counts row-major into n(n+1)/2 int32 (every count must be
  * < 2^31), and unpack it back (overwriting the upper triangle). */
