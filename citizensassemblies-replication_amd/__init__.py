@@ -37,6 +37,12 @@ rows): PanelSet's set operators and comparisons, legacy_panel_comparison(instanc
 seeds and their PanelComparison (shared panels, held-out coverage, overlap, cross-sample collision) --
 and legacy_portfolio_overlap, a run beside a LEXIMIN / XMIN portfolio (PortfolioOverlap)
 
+plus a weight per agent against such a table (csa_rows_price_async / csa_rows_mw_cover_async /
+csa_rows_first_holder_async): PanelDistribution.price(weights) -- the drawn panel with the largest weight
+sum, the heuristic pricing step of LEXIMIN / XMIN's column generation --, initial_committees(rounds), the
+reference's multiplicative-weights stage over the drawn panels (legacy_initial_committees), and
+legacy_price over fresh draws that are not kept; rows_*_host are the numpy contracts
+
 plus xmin._get_panel_not_in_portfolio_if_possible (XMIN's LEGACY caller,
 xmin.py:464-474) on the device.
 """
@@ -54,6 +60,9 @@ from .stats import PanelDistribution, panel_multiplicities_host  # noqa: F401
 from .analysis import legacy_panel_comparison, legacy_portfolio_overlap  # noqa: F401
 from .stats import (PanelComparison, PortfolioOverlap, compare_panel_distributions, portfolio_overlap,  # noqa: F401
                     rows_find_host, rows_join_host)
+from .analysis import legacy_initial_committees, legacy_price  # noqa: F401
+from .stats import (PanelPrice, rows_first_holder_host, rows_mw_cover_host, rows_price_host,  # noqa: F401
+                    rows_score_host)
 from . import _native, xmin  # noqa: F401
 
 __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_cats",
@@ -65,4 +74,6 @@ __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_c
            "composition_difference", "group_whist_host", "portfolio_group_composition",
            "legacy_panel_distribution", "PanelDistribution", "panel_multiplicities_host",
            "legacy_panel_comparison", "legacy_portfolio_overlap", "PanelComparison", "PortfolioOverlap",
-           "compare_panel_distributions", "portfolio_overlap", "rows_join_host", "rows_find_host"]
+           "compare_panel_distributions", "portfolio_overlap", "rows_join_host", "rows_find_host",
+           "legacy_initial_committees", "legacy_price", "PanelPrice", "rows_score_host", "rows_price_host",
+           "rows_mw_cover_host", "rows_first_holder_host"]

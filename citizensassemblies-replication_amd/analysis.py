@@ -954,6 +954,61 @@ def legacy_panel_comparison(instance: Instance, iterations: int, seed_a: int = 0
     return run_a, run_b, compare_panel_distributions(run_a[3], run_b[3])
 
 
+def legacy_initial_committees(instance: Instance, iterations: int, random_seed: int, rounds: int = None, *,
+                              rng: str = None):
+    """The reference's _generate_initial_committees (xmin.py:229-290) over a LEGACY run's distinct panels instead
+    of an ILP: ``legacy_panel_distribution(instance, iterations, random_seed, rng=rng)`` followed by its
+    ``initial_committees(rounds)`` (``rounds`` defaults to 3 n, leximin.py:373; csa_rows_mw_cover_async and
+    csa_rows_first_holder_async over the run's sorted table on the device).  Returns ``(committees,
+    covered_agents, output_lines)``, what _expand_distribution_leximin takes as ``initial_committees`` /
+    ``initial_covered_agents``.  World size > 1 raises NotImplementedError, as ``legacy_panel_distribution``."""
+    return legacy_panel_distribution(instance, iterations, random_seed, rng=rng)[3].initial_committees(rounds)
+
+
+def legacy_price(instance: Instance, weights, iterations: int, random_seed: int, chunk: int = 1 << 20):
+    """Heuristic pricing over fresh draws that are not kept: among the panels [0, ``iterations``) of the LEGACY
+    stream of ``random_seed``, the one with the largest weight sum.  Returns ``(frozenset of agent ids, value,
+    global draw index)``; ties go to the lowest draw index, so the result does not depend on ``chunk``;
+    ``(frozenset(), -inf, None)`` for no draws.
+
+    ``weights`` as ``PanelDistribution.price`` takes them (KeyError / ValueError before anything is enqueued).
+    Chunks of ``chunk`` panels are drawn on the current device (``distributed.device_redraw``'s
+    ``device_chunk``: csa_redraw_async) and each is scored where it lies with csa_rows_price_async(index_base =
+    the chunk's offset, CSA_PRICE_ACCUMULATE); one host wait at the end, for the status block and the best pair;
+    then the one winning panel is drawn again by its index.  A drawn panel whose value exceeds the LP's bound is a
+    violated dual constraint found without an ILP call (xmin.py:410-440).  One process: with world size > 1
+    this call raises NotImplementedError."""
+    import torch
+    from . import distributed as D
+    from .stats import PRICE_NONE, RowTable, weight_vector
+    if D.world_size() > 1:
+        raise NotImplementedError("legacy_price: sharded runs (world size %d) are not supported; price on one "
+                                  "process" % D.world_size())
+    enc = encode_cached(instance.categories, instance.agents)
+    w = weight_vector(weights, enc.agent_ids)
+    S, chunk = int(iterations), max(1, int(chunk))
+    seed(random_seed)
+    enc.check_quotas(instance.k)
+    STREAM.take_panels(S)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    draw = D.device_redraw(enc, instance.k, random_seed, dev)
+    ops = draw.tables()
+    with torch.cuda.device(dev), torch.cuda.stream(ops.stream):
+        d_w = torch.from_numpy(w).to(dev)
+        best = torch.tensor([-1, np.array([-np.inf]).view(np.int64)[0]], dtype=torch.int64, device=dev)
+        for off in range(0, S, chunk):
+            c = min(chunk, S - off)
+            length = torch.full((1,), c, dtype=torch.int64, device=dev)
+            ops.price(RowTable(draw.device_chunk(off, c), None, None, length, c, enc.W), enc.n, d_w, off, best)
+        h = torch.cat([draw.status.view(torch.int64), best]).cpu().numpy()
+    N.raise_status(h[:2].view(np.uint32))
+    at = int(h[2:3].view(np.uint64)[0])
+    if at == PRICE_NONE:
+        return frozenset(), float("-inf"), None
+    row = np.ascontiguousarray(draw(at, 1), np.uint64).reshape(-1)
+    return frozenset(enc.agent_ids[q] for q in unpack_panel(row, enc.n)), float(h[3:4].view(np.float64)[0]), at
+
+
 def legacy_portfolio_overlap(instance: Instance, distribution, portfolio, probabilities):
     """A LEGACY run's ``stats.PanelDistribution`` beside a LEXIMIN / XMIN ``(portfolio, probabilities)``: how
     much of LEGACY's mass lies on the portfolio's panels and how much of the portfolio's on panels LEGACY ever

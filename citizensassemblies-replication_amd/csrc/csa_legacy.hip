@@ -3927,3 +3927,100 @@ int csa_rows_find_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t 
 }
 
 }  // extern "C"
+
+// Pricing over such tables (rows_price.inc) stands last, for the same reason.
+namespace {
+#include "rows_price.inc"
+
+// what the three entry points check alike; 0 or the error
+int rp_check(const char *who, const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n) {
+    if (W < 1 || !d_len) return fail(CSA_E_INVALID, "%s: bad arguments", who);
+    if (n <= 0 || (int64_t)n > (int64_t)64 * W)
+        return fail(CSA_E_INVALID, "%s: n = %d agents do not fit rows of %d words", who, n, W);
+    if (cap && !d_rows) return fail(CSA_E_INVALID, "%s: NULL rows with a non-zero capacity", who);
+    if (cap >= (1ull << 32) - 1) return fail(CSA_E_UNSUPPORTED, "%s: cap >= 2^32 - 1 (u32 row indices)", who);
+    if (rp_score_lds(W) > 160 * 1024) return fail(CSA_E_UNSUPPORTED, "%s: W = %d needs %zu B of LDS", who, W, rp_score_lds(W));
+    return CSA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+uint64_t csa_rows_price_tile(void) { return kRpTile; }
+
+uint64_t csa_rows_price_scratch_bytes(uint64_t cap, int32_t W) {
+    (void)W;
+    return 16 * rp_blocks(cap);
+}
+
+int csa_rows_price_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                         const double *d_weights, uint64_t index_base, uint32_t flags, double *d_scores,
+                         uint64_t *d_best, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+    if (int rc = rp_check("rows price", d_rows, d_len, cap, W, n)) return rc;
+    if (!d_weights || !d_best) return fail(CSA_E_INVALID, "rows price: NULL weights or d_best");
+    if (flags & ~CSA_PRICE_ACCUMULATE) return fail(CSA_E_INVALID, "rows price: unknown flags 0x%x", flags);
+    const uint64_t nb = rp_blocks(cap);
+    if (nb && (!d_scratch || scratch_bytes < 16 * nb || ((uintptr_t)d_scratch & 7)))
+        return fail(CSA_E_INVALID, "rows price: scratch_bytes < csa_rows_price_scratch_bytes, or scratch NULL or not "
+                                   "8-byte aligned");
+    if (rs_overlap(d_best, 16, d_len, 8) || rs_overlap(d_scores, cap * 8, d_rows, cap * W * 8) ||
+        rs_overlap(d_scores, cap * 8, d_weights, (uint64_t)n * 8) || rs_overlap(d_scores, cap * 8, d_len, 8))
+        return fail(CSA_E_INVALID, "rows price: an output aliases an input");
+    const hipStream_t st = (hipStream_t)stream;
+    uint64_t *slab = static_cast<uint64_t *>(d_scratch);
+    if (nb)
+        hipLaunchKernelGGL(rp_score_kernel<>, dim3((unsigned)nb), dim3(kRpThreads), rp_score_lds(W), st, d_rows,
+                           reinterpret_cast<const unsigned long long *>(d_len), cap, (int)W, (int)n, d_weights, d_scores,
+                           slab);
+    hipLaunchKernelGGL(rp_best_kernel<>, dim3(1), dim3(kRpThreads), kRpBestLds, st, (const uint64_t *)slab, nb,
+                       index_base, (int)(flags & CSA_PRICE_ACCUMULATE), d_best);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+int csa_rows_mw_cover_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                            uint32_t rounds, double *d_weights, uint8_t *d_chosen, uint32_t *d_picks,
+                            double *d_pick_scores, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+    if (int rc = rp_check("rows mw cover", d_rows, d_len, cap, W, n)) return rc;
+    if (!d_weights || (cap && !d_chosen) || (rounds && !d_picks))
+        return fail(CSA_E_INVALID, "rows mw cover: NULL weights, chosen or picks");
+    const uint64_t nb = rp_blocks(cap);
+    if (nb && (!d_scratch || scratch_bytes < 16 * nb || ((uintptr_t)d_scratch & 7)))
+        return fail(CSA_E_INVALID, "rows mw cover: scratch_bytes < csa_rows_price_scratch_bytes, or scratch NULL or "
+                                   "not 8-byte aligned");
+    if (rs_overlap(d_weights, (uint64_t)n * 8, d_rows, cap * W * 8) || rs_overlap(d_chosen, cap, d_rows, cap * W * 8) ||
+        rs_overlap(d_picks, (uint64_t)rounds * 4, d_rows, cap * W * 8) || rs_overlap(d_weights, (uint64_t)n * 8, d_len, 8) ||
+        rs_overlap(d_chosen, cap, d_len, 8) || rs_overlap(d_picks, (uint64_t)rounds * 4, d_len, 8))
+        return fail(CSA_E_INVALID, "rows mw cover: an output aliases the table");
+    const hipStream_t st = (hipStream_t)stream;
+    uint64_t *slab = static_cast<uint64_t *>(d_scratch);
+    for (uint32_t r = 0; r < rounds; ++r) {
+        if (nb)
+            hipLaunchKernelGGL(rp_score_kernel<>, dim3((unsigned)nb), dim3(kRpThreads), rp_score_lds(W), st, d_rows,
+                               reinterpret_cast<const unsigned long long *>(d_len), cap, (int)W, (int)n,
+                               (const double *)d_weights, (double *)nullptr, slab);
+        hipLaunchKernelGGL(rp_round_kernel<>, dim3(1), dim3(kRpThreads), rp_round_lds(W), st, d_rows, (int)W, (int)n,
+                           (const uint64_t *)slab, nb, d_weights, d_chosen, d_picks, d_pick_scores, r);
+    }
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+int csa_rows_first_holder_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                                uint32_t *d_first_row, void *stream) {
+    if (int rc = rp_check("rows first holder", d_rows, d_len, cap, W, n)) return rc;
+    if (!d_first_row) return fail(CSA_E_INVALID, "rows first holder: NULL output");
+    if (rs_overlap(d_first_row, (uint64_t)n * 4, d_rows, cap * W * 8) || rs_overlap(d_first_row, (uint64_t)n * 4, d_len, 8))
+        return fail(CSA_E_INVALID, "rows first holder: the output aliases the table");
+    const hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(d_first_row, 0xFF, (size_t)n * 4, st));
+    if (cap == 0) return CSA_OK;
+    const uint64_t words = cap * (uint64_t)W;
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((words + 8 * kRpThreads - 1) / (8 * kRpThreads), 2048));
+    hipLaunchKernelGGL(rp_first_holder_kernel<>, dim3(grid), dim3(kRpThreads), (size_t)64 * W * 4, st, d_rows,
+                       reinterpret_cast<const unsigned long long *>(d_len), cap, (int)W, (int)n, d_first_row);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+}  // extern "C"

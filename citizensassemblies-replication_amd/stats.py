@@ -15,6 +15,7 @@
 """
 import contextlib
 import ctypes
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -740,6 +741,72 @@ class PanelDistribution:
         self._table = t
         return t
 
+    def price(self, weights, scores=False):
+        """The distinct panel with the largest weight sum, as a ``PanelPrice``: heuristic pricing of column
+        generation over the panels this run drew.  ``weights``: a mapping agent id -> float covering every agent
+        (KeyError otherwise) or a sequence in the instance's agent order; a weight that is not finite raises
+        ValueError before anything is enqueued.  A table on a device is priced there (csa_rows_price_async:
+        float64 sums in ascending agent order, ties to the lowest row of the sorted table; one host wait, for the
+        best row's words), a host table through ``rows_price_host``.  ``scores=True`` returns ``(price,
+        scores)``, the per-row scores left on the table's device as a float64 tensor (a numpy array for a host
+        table)."""
+        w = weight_vector(weights, self._ids)
+        if not self.distinct:
+            out = PanelPrice(frozenset(), float("-inf"), None, None, 0)
+            return (out, np.zeros(0, np.float64)) if scores else out
+        t = self.table()
+        ops, device = _table_ops(t)
+        best, sc = ops.price(t, self._n, w, scores=scores)
+        if device:
+            import torch
+            with torch.cuda.stream(ops.stream):
+                at = (best[:1] & 0xFFFFFFFF).clamp(0, t.cap - 1)
+                lists = torch.stack([t.first, t.mult]).to(torch.int64)[:, at].reshape(-1) & 0xFFFFFFFF
+                h = torch.cat([best, lists, t.rows.view(t.cap, t.W)[at].reshape(-1)]).cpu().numpy()
+            sc = None if sc is None else sc[:self.distinct]
+        else:
+            at = min(int(best[0]), t.cap - 1)
+            h = np.concatenate([best.view(np.int64), [int(t.first[at]), int(t.mult[at])],
+                                np.asarray(t.rows).view(np.int64).reshape(-1, t.W)[at]])
+        out = PanelPrice(frozenset(self._decode(h[4:].view(np.uint64))), float(h[1:2].view(np.float64)[0]), int(h[0]),
+                         int(h[2]), int(h[3]))
+        return (out, sc) if scores else out
+
+    def initial_committees(self, rounds=None):
+        """The reference's _generate_initial_committees (xmin.py:229-290, leximin.py:236-300) over the panels this
+        run drew instead of an ILP over all feasible ones: ``rounds`` (default 3 n, leximin.py:373)
+        multiplicative-weights rounds over the table -- on its device, csa_rows_mw_cover_async, two launches a
+        round and no wait between them --, then every agent no pick covers gets the lowest row holding it
+        (csa_rows_first_holder_async).  Returns ``(committees, covered_agents, output_lines)``, what
+        _expand_distribution_leximin takes as ``initial_committees`` / ``initial_covered_agents``; the lines say
+        which agents no drawn panel contains.  One host wait."""
+        n = self._n
+        rounds = 3 * n if rounds is None else int(rounds)
+        if rounds < 0:
+            raise ValueError("rounds must not be negative")
+        if not self.distinct:
+            none = np.full(n, NO_ROW, np.int64)
+            return committees_from_cover(none[:0], none, none[:0], none, n, list(self._ids))
+        t = self.table()
+        ops, device = _table_ops(t)
+        if device:
+            import torch
+            with torch.cuda.stream(ops.stream):
+                w = torch.ones(n, dtype=torch.float64, device=ops.device)
+                chosen = torch.zeros(t.cap, dtype=torch.uint8, device=ops.device)
+                picks, _ = ops.mw_cover(t, n, rounds, w, chosen)
+                first = ops.first_holder(t, n)
+                h = torch.cat([picks.to(torch.int64) & 0xFFFFFFFF, first.to(torch.int64) & 0xFFFFFFFF,
+                               _rows_at(t, picks, True).reshape(-1), _rows_at(t, first, True).reshape(-1)]).cpu().numpy()
+            picks, first = h[:rounds], h[rounds:rounds + n]
+            picked = h[rounds + n:rounds + n + rounds * t.W].reshape(rounds, t.W)
+            holders = h[rounds + n + rounds * t.W:].reshape(n, t.W)
+        else:
+            picks, _ = ops.mw_cover(t, n, rounds, np.ones(n, np.float64), np.zeros(t.cap, np.uint8))
+            first = ops.first_holder(t, n)
+            picked, holders = _rows_at(t, picks, False), _rows_at(t, first, False)
+        return committees_from_cover(picks, first, picked, holders, n, list(self._ids))
+
     def __getstate__(self):
         f, m = self.multiplicities()
         rows = self._panel_rows(np.arange(self.distinct)) if self._panels is not None else None
@@ -1005,6 +1072,30 @@ class HostRowTables:
     def find(self, table, queries):
         return rows_find_host(table.rows[:min(int(table.length[0]), table.cap)], queries)
 
+    def _valid(self, table):
+        return np.asarray(table.rows).view(np.uint64).reshape(-1, table.W)[:min(int(table.length[0]), table.cap)]
+
+    def price(self, table, n, weights, index_base=0, best=None, scores=False):
+        """rows_price_host over the table's first ``length`` rows: ``(best uint64[2], scores or None)``, the
+        best as csa_rows_price_async leaves it (index, score bits); ``best`` given: accumulated onto, in place."""
+        w = np.asarray(weights, np.float64).reshape(-1)[:n]
+        old = None if best is None else (int(best[0]), float(best[1:2].view(np.float64)[0]))
+        at, value, sc = rows_price_host(self._valid(table), w, index_base, old)
+        out = np.zeros(2, np.uint64) if best is None else best
+        out[0], out[1:2].view(np.float64)[0] = at, value
+        return out, (sc if scores else None)
+
+    def mw_cover(self, table, n, rounds, weights, chosen, pick_scores=False):
+        """rows_mw_cover_host; ``weights`` (float64[n]) and ``chosen`` (uint8[cap]) are updated in place.  Returns
+        ``(picks int64[rounds], pick scores or None)``."""
+        d = min(int(table.length[0]), table.cap)
+        picks, w, ch, ps = rows_mw_cover_host(self._valid(table), weights[:n], chosen[:d], rounds)
+        weights[:n], chosen[:d] = w, ch
+        return picks, (ps if pick_scores else None)
+
+    def first_holder(self, table, n):
+        return rows_first_holder_host(self._valid(table), n)
+
     def read(self, table, lists, draw_status=None):
         d = min(int(table.length[0]), table.cap)
         words = np.concatenate([np.zeros(4, np.uint32) if draw_status is None else np.asarray(draw_status, np.uint32),
@@ -1091,6 +1182,15 @@ class DeviceRowTables:
 
     def find(self, table, d_queries, n_queries):
         return rows_find_device(table, d_queries, n_queries, self.stream)
+
+    def price(self, table, n, weights, index_base=0, best=None, scores=False):
+        return rows_price_device(table, n, weights, self.stream, index_base, best, scores)
+
+    def mw_cover(self, table, n, rounds, weights, chosen, pick_scores=False):
+        return rows_mw_cover_device(table, n, rounds, weights, chosen, self.stream, pick_scores)
+
+    def first_holder(self, table, n):
+        return rows_first_holder_device(table, n, self.stream)
 
     def read(self, table, lists, draw_status=None):
         """The one host wait: [draw status | table status | length], then the D rows (and lists)."""
@@ -1254,6 +1354,253 @@ def _table_counts(table, queries):
     at = rows_find_host(table.rows[:d], q)
     mult = np.concatenate([np.asarray(table.mult[:d], np.int64) & 0xFFFFFFFF, [0]])
     return mult[np.where(at == FIND_MISSING, d, at)]
+
+
+# --- a weight per agent against a table (csrc/rows_price.inc) ------------------------------------------------
+# Which panel of a table has the largest weight sum: the question both loops of the reference's column
+# generation put to an ILP (xmin.py:229-290 with multiplicative weights, xmin.py:410-440 with the dual values),
+# answered over panels that were drawn.  ``rows_score_host``, ``rows_price_host``, ``rows_mw_cover_host`` and
+# ``rows_first_holder_host`` are the numpy contracts of csa_rows_price_async, csa_rows_mw_cover_async and
+# csa_rows_first_holder_async, bit for bit.
+
+PRICE_NONE = 0xFFFFFFFFFFFFFFFF
+NO_ROW = 0xFFFFFFFF
+
+
+def _price_input(rows, weights):
+    p = np.ascontiguousarray(rows, np.uint64)
+    w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    if p.ndim != 2:
+        raise ValueError("rows must be uint64[n, W]")
+    if not 0 < len(w) <= 64 * p.shape[1]:
+        raise ValueError("%d weights do not fit rows of %d words" % (len(w), p.shape[1]))
+    return p, w
+
+
+def _member_columns(p, n):
+    """bool[n, D]: column i = which rows hold agent i."""
+    if not len(p):
+        return np.zeros((n, 0), np.bool_)
+    return np.ascontiguousarray(np.unpackbits(p.view(np.uint8), axis=1, bitorder="little")[:, :n].T).astype(np.bool_)
+
+
+def _score_columns(cols, w):
+    s = np.zeros(cols.shape[1], np.float64)
+    with np.errstate(all="ignore"):
+        for i in range(len(w)):
+            np.add(s, w[i], out=s, where=cols[i])      # s = np.where(bit, s + w[i], s)
+    return s
+
+
+def rows_score_host(rows, weights):
+    """float64[D]: per row the sum of ``weights[i]`` over its set bits i, from +0.0, one rounded add per member
+    in ascending agent index -- rp_score_kernel's contract.  Agents 0..n-1 in turn over the whole column:
+    ``s = np.where(bit, s + w[i], s)``."""
+    p, w = _price_input(rows, weights)
+    return _score_columns(_member_columns(p, len(w)), w)
+
+
+def _best_of(sc):
+    """(row, value) of the first maximum of the scores by ``>``, or (PRICE_NONE, -inf)."""
+    if len(sc) and not np.isnan(sc).any():
+        at = int(np.argmax(sc))                 # the first maximum
+        return at, float(sc[at])
+    at, value = PRICE_NONE, -np.inf
+    for d in range(len(sc)):
+        if at == PRICE_NONE or sc[d] > value:
+            at, value = d, float(sc[d])
+    return at, value
+
+
+def rows_price_host(rows, weights, index_base=0, best=None):
+    """csa_rows_price_async's contract: ``(index, value, scores)`` -- ``index_base`` + the row of the greatest
+    score (compared as float64 values with >, ties to the lowest row) and that score; (PRICE_NONE, -inf) for
+    an empty table.  ``best`` = a stored ``(index, value)``: CSA_PRICE_ACCUMULATE, the stored pair is replaced
+    only by a strictly greater score, or when its index is PRICE_NONE."""
+    sc = rows_score_host(rows, weights)
+    at, value = _best_of(sc)
+    if at != PRICE_NONE:
+        at += int(index_base)
+    if best is not None and (at == PRICE_NONE or not (int(best[0]) == PRICE_NONE or value > best[1])):
+        at, value = int(best[0]), float(best[1])
+    return at, value, sc
+
+
+def weights_sum_host(weights, W):
+    """The lane-strided sum of rp_round_kernel: the vector padded with +0.0 to 64 * W entries, its 64-wide
+    rows added one after another from +0.0, then the 64 partial sums added left to right from +0.0."""
+    wp = np.zeros(64 * W, np.float64)
+    wp[:len(weights)] = weights
+    partial = np.zeros(64, np.float64)
+    for j in range(W):
+        partial = partial + wp[64 * j:64 * j + 64]
+    s = np.float64(0.0)
+    for x in partial:
+        s = s + x
+    return s
+
+
+def rows_mw_cover_host(rows, weights, chosen, rounds):
+    """csa_rows_mw_cover_async's contract: ``rounds`` multiplicative-weights rounds over the table, from
+    ``weights`` (float64[n]) and ``chosen`` (one flag per row).  Returns ``(picks int64[rounds], weights,
+    chosen uint8[D], pick_scores float64[rounds])``, the inputs unchanged.  Per round, in the order of
+    xmin.py:251-266: the best row p under the weights; its members' weights times 0.8; all weights times
+    n / (their lane-strided sum); then, p chosen before: all weights 0.9 w + 0.1 (product and sum rounded
+    apart), else p becomes chosen.  An empty table leaves the weights alone and picks NO_ROW."""
+    p, w = _price_input(rows, weights)
+    w = w.copy()
+    n, W = len(w), p.shape[1]
+    ch = np.array(chosen, np.uint8).reshape(-1).copy()
+    if len(ch) != len(p):
+        raise ValueError("one chosen flag per row")
+    picks, ps = np.full(int(rounds), NO_ROW, np.int64), np.full(int(rounds), -np.inf, np.float64)
+    cols = _member_columns(p, n)
+    for r in range(int(rounds)):
+        if not len(p):
+            continue
+        at, value = _best_of(_score_columns(cols, w))
+        picks[r], ps[r] = at, value
+        w = np.where(cols[:, at], w * 0.8, w)
+        w = w * (np.float64(n) / weights_sum_host(w, W))
+        if ch[at]:
+            w = 0.9 * w + 0.1
+        ch[at] = 1
+    return picks, w, ch, ps
+
+
+def rows_first_holder_host(rows, n):
+    """int64[n]: the lowest row holding agent i, or NO_ROW -- csa_rows_first_holder_async's contract."""
+    p = np.ascontiguousarray(rows, np.uint64)
+    if p.ndim != 2 or not 0 < n <= 64 * p.shape[1]:
+        raise ValueError("rows must be uint64[D, W] with 0 < n <= 64 W")
+    if not len(p):
+        return np.full(n, NO_ROW, np.int64)
+    member = np.unpackbits(p.view(np.uint8), axis=1, bitorder="little")[:, :n].astype(bool)
+    return np.where(member.any(axis=0), member.argmax(axis=0), NO_ROW).astype(np.int64)
+
+
+def rows_price_device(table, n, d_weights, stream, index_base=0, best=None, scores=False):
+    """Enqueue csa_rows_price_async over RowTable ``table`` (its length read on the device) with the float64
+    device tensor ``d_weights`` (host weights are uploaded on the stream) on ``stream``; nothing waits.  Returns
+    ``(best, scores)``: int64[2] on the device -- ``index_base`` + the best row, the score's bits -- and the
+    float64[cap] scores, or None unless ``scores``.  ``best`` given: CSA_PRICE_ACCUMULATE onto that tensor.  The
+    scratch comes from torch's allocator on that stream."""
+    import torch
+    L = N.lib()
+    dev = table.length.device
+    with torch.cuda.stream(stream):
+        if not _is_device_tensor(d_weights):
+            d_weights = torch.from_numpy(np.ascontiguousarray(d_weights, np.float64)).to(dev)
+        need = int(L.csa_rows_price_scratch_bytes(table.cap, table.W))
+        scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        sc = torch.empty(max(table.cap, 1), dtype=torch.float64, device=dev) if scores else None
+        flags = N.CSA_PRICE_ACCUMULATE if best is not None else 0
+        if best is None:
+            best = torch.empty(2, dtype=torch.int64, device=dev)
+    N.check(L.csa_rows_price_async(N.ptr(table.rows), N.ptr(table.length), table.cap, table.W, int(n), N.ptr(d_weights),
+                                   int(index_base), flags, N.ptr(sc), N.ptr(best), N.ptr(scratch), need,
+                                   ctypes.c_void_p(stream.cuda_stream)))
+    return best, sc
+
+
+def rows_mw_cover_device(table, n, rounds, d_weights, d_chosen, stream, pick_scores=False):
+    """Enqueue csa_rows_mw_cover_async: ``rounds`` rounds over RowTable ``table`` on ``stream``, 2 launches each,
+    nothing waits.  ``d_weights`` (float64[n]) and ``d_chosen`` (uint8[cap]) are device tensors, read and
+    written.  Returns ``(picks, pick scores)``: int32 of ``rounds`` uint32 words, and float64 or None."""
+    import torch
+    L = N.lib()
+    dev = table.length.device
+    rounds = int(rounds)
+    with torch.cuda.stream(stream):
+        need = int(L.csa_rows_price_scratch_bytes(table.cap, table.W))
+        scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        picks = torch.empty(max(rounds, 1), dtype=torch.int32, device=dev)
+        ps = torch.empty(max(rounds, 1), dtype=torch.float64, device=dev) if pick_scores else None
+    N.check(L.csa_rows_mw_cover_async(N.ptr(table.rows), N.ptr(table.length), table.cap, table.W, int(n), rounds,
+                                      N.ptr(d_weights), N.ptr(d_chosen), N.ptr(picks), N.ptr(ps), N.ptr(scratch), need,
+                                      ctypes.c_void_p(stream.cuda_stream)))
+    return picks[:rounds], (ps[:rounds] if pick_scores else None)
+
+
+def rows_first_holder_device(table, n, stream):
+    """Enqueue csa_rows_first_holder_async over RowTable ``table`` on ``stream``; nothing waits.  Returns an int32
+    tensor of n uint32 words: the lowest row holding each agent, or NO_ROW."""
+    import torch
+    with torch.cuda.stream(stream):
+        out = torch.empty(int(n), dtype=torch.int32, device=table.length.device)
+    N.check(N.lib().csa_rows_first_holder_async(N.ptr(table.rows), N.ptr(table.length), table.cap, table.W, int(n),
+                                                N.ptr(out), ctypes.c_void_p(stream.cuda_stream)))
+    return out
+
+
+PanelPrice = namedtuple("PanelPrice", "panel value row first multiplicity")
+PanelPrice.__doc__ = """The best distinct panel of a run under a weight per agent: ``panel`` (frozenset of agent
+ids), ``value`` (its weight sum), ``row`` (its row in the run's sorted table), ``first`` (its lowest draw index)
+and ``multiplicity``.  An empty run: (frozenset(), -inf, None, None, 0)."""
+
+
+def weight_vector(weights, agent_ids):
+    """float64[n] in the instance's agent order from a mapping agent id -> weight (KeyError for an agent it
+    lacks) or a sequence of n weights; ValueError for another length or a weight that is not finite."""
+    ids = list(agent_ids)
+    if hasattr(weights, "keys"):
+        w = np.array([weights[aid] for aid in ids], np.float64)
+    else:
+        w = np.array(weights, np.float64).reshape(-1)
+        if len(w) != len(ids):
+            raise ValueError("%d weights for %d agents" % (len(w), len(ids)))
+    if not np.isfinite(w).all():
+        raise ValueError("weights must be finite")
+    return w
+
+
+def _table_ops(table):
+    """(operations, on the device?) for a RowTable: DeviceRowTables on its device's current stream, or
+    HostRowTables."""
+    if _is_device_tensor(table.rows):
+        import torch
+        dev = table.rows.device
+        return DeviceRowTables(dev, torch.cuda.current_stream(dev)), True
+    return HostRowTables(), False
+
+
+def _rows_at(table, index, device):
+    """The table's rows at ``index`` (clamped into the table: NO_ROW entries give some row, to be ignored),
+    [len(index), W] as int64 words; nothing waits."""
+    if device:
+        at = (index.to(table.rows.dtype) & 0xFFFFFFFF).clamp(0, table.cap - 1)
+        return table.rows.view(table.cap, table.W)[at]
+    at = np.clip(np.asarray(index, np.int64) & 0xFFFFFFFF, 0, table.cap - 1)
+    return np.asarray(table.rows).view(np.int64).reshape(-1, table.W)[at]
+
+
+def committees_from_cover(picks, first_row, picked_rows, holder_rows, n, agent_ids):
+    """The reference's return of _generate_initial_committees from a cover over a table: the picked rows are
+    the committees of the multiplicative-weights stage; then, agents in order, each one no committee covers yet
+    gets the lowest row holding it (which covers that row's members too), the counterpart of xmin.py:272-282.
+    ``(committees, covered_agents, output_lines)``."""
+    from .instance import unpack_panel
+    committees, covered, lines = set(), set(), []
+    decode = lambda row: frozenset(agent_ids[q] for q in unpack_panel(np.ascontiguousarray(row).view(np.uint64), n))
+    seen = set()
+    for r, p in enumerate(np.asarray(picks, np.int64).tolist()):
+        if p != NO_ROW and p not in seen:
+            seen.add(p)
+            c = decode(picked_rows[r])
+            committees.add(c)
+            covered |= c
+    for i, aid in enumerate(agent_ids):
+        if aid in covered:
+            continue
+        if int(first_row[i]) == NO_ROW:
+            lines.append("Agent %s not contained in any drawn panel." % (aid,))
+            continue
+        c = decode(holder_rows[i])
+        committees.add(c)
+        covered |= c
+    if len(covered) == len(agent_ids):
+        lines.append("All agents are contained in some drawn panel.")
+    return committees, frozenset(covered), lines
 
 
 class PanelComparison:

@@ -552,6 +552,60 @@ int csa_rows_join_async(const uint64_t *d_a_rows, const uint32_t *d_a_mult /* or
 int csa_rows_find_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W,
                         const uint64_t *d_queries, uint64_t n_queries, uint32_t *d_out_index, void *stream);
 
+/* A weight per agent against a table of panels: which row has the largest weight sum?  Both loops of the
+ * reference's column generation put that question to an ILP over all feasible panels -- the
+ * multiplicative-weights stage of _generate_initial_committees (xmin.py:229-290, leximin.py:236-300) 3 n
+ * times, the inner loop of _expand_distribution_leximin (xmin.py:410-440) once per LP iteration with the
+ * dual values.  These entry points answer it over panels that were DRAWN (a run's table of distinct panels,
+ * or chunks of fresh draws): heuristic pricing, no ILP and no LP.  All are stream-ordered, read the length
+ * on the device, wait for nothing and allocate nothing.
+ *
+ * Table: d_rows uint64[cap][W] in the tables' row form (agent p = bit p & 63 of word p >> 6, padding bits
+ * zero), min(*d_len, cap) valid rows; a row past the length is never read.  n agents, 0 < n <= 64 * W.
+ * d_weights: n float64.
+ *
+ * Price: score of row d = the sum of d_weights[i] over the set bits i of row d, in float64, starting from
+ * +0.0 with one rounded add per member in ASCENDING agent index (no reassociation: a host loop gives the
+ * same bits).  d_scores (cap float64, or NULL) receives the scores of the valid rows; entries past the
+ * length are not written.  d_best (2 uint64, required) receives index_base + the best row and its score's
+ * bits: scores compare as float64 values with >, ties go to the lowest row.  An empty table gives
+ * CSA_PRICE_NONE and -inf.  With CSA_PRICE_ACCUMULATE in flags the stored d_best is replaced only by a
+ * strictly greater score, or when it holds CSA_PRICE_NONE (an empty table then leaves it as it is): chunks
+ * priced in ascending index order keep the lowest global index among ties, whatever the chunk size.
+ * d_scratch: csa_rows_price_scratch_bytes(cap, W) bytes, 8-byte aligned (one (row, score) per
+ * csa_rows_price_tile() rows).
+ *
+ * MW cover: `rounds` rounds of the multiplicative-weights stage over the table, each a price pass and one
+ * workgroup's update, 2 * rounds plain launches with no host wait between them.  Round r: p = the best row
+ * under d_weights; d_picks[r] = p (uint32); d_pick_scores[r] (or NULL) = its score; w[i] *= 0.8 for the
+ * members of row p; s = the lane-strided sum of w (partial[l] = sum over ascending j of w[64 j + l] from
+ * +0.0 over the array padded with +0.0 to 64 * W entries, then s = the sum over ascending l of partial[l]
+ * from +0.0); f = n / s; w[i] *= f for all i; then if d_chosen[p] (uint8 per row) was set, w[i] = 0.9 *
+ * w[i] + 0.1 for all i with the product and the sum rounded separately, else d_chosen[p] = 1 -- the order
+ * of xmin.py:251-266.  d_weights and d_chosen are read and written, so a second call continues the first.
+ * An empty table leaves the weights alone and writes 0xFFFFFFFF picks (and -inf pick scores).  rounds == 0
+ * launches nothing.  The scratch is the price pass's.
+ *
+ * First holder: d_first_row[i] (n uint32) = the lowest valid row whose bit i is set, or 0xFFFFFFFF.
+ *
+ * CSA_E_UNSUPPORTED for cap >= 2^32 - 1 or a W whose weights exceed the LDS.  CSA_E_INVALID, before any
+ * device call, for W < 1, n <= 0, n > 64 * W, a NULL d_len, NULL rows with a non-zero capacity, a NULL
+ * weights / d_best / d_chosen / d_picks / d_first_row where one is needed, unknown flags, a scratch that is
+ * NULL, short or misaligned with cap > 0, or an output overlapping the table or its length. */
+#define CSA_PRICE_ACCUMULATE 0x1u
+#define CSA_PRICE_NONE 0xFFFFFFFFFFFFFFFFull
+uint64_t csa_rows_price_tile(void);
+uint64_t csa_rows_price_scratch_bytes(uint64_t cap, int32_t W);
+int csa_rows_price_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                         const double *d_weights, uint64_t index_base, uint32_t flags, double *d_scores /* or NULL */,
+                         uint64_t *d_best, void *d_scratch, uint64_t scratch_bytes, void *stream);
+int csa_rows_mw_cover_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                            uint32_t rounds, double *d_weights, uint8_t *d_chosen, uint32_t *d_picks,
+                            double *d_pick_scores /* or NULL */, void *d_scratch, uint64_t scratch_bytes,
+                            void *stream);
+int csa_rows_first_holder_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                                uint32_t *d_first_row, void *stream);
+
 /* Multi-GPU pair exchange: pack the upper triangle incl. the diagonal of the
  * n*n int64 pair counts row-major into n(n+1)/2 int32 (every count must be
  * < 2^31), and unpack it back (overwriting the upper triangle). */
