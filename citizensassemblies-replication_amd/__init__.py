@@ -43,6 +43,11 @@ sum, the heuristic pricing step of LEXIMIN / XMIN's column generation --, initia
 reference's multiplicative-weights stage over the drawn panels (legacy_initial_committees), and
 legacy_price over fresh draws that are not kept; rows_*_host are the numpy contracts
 
+plus the maximin lottery over such a table (csa_rows_maximin_async): PanelDistribution.maximin(rounds) /
+legacy_maximin -- how fair a lottery over exactly the drawn panels can be made, the reference's first leximin
+stage over them solved by multiplicative weights with a lower and an upper bound (PanelMaximin), no LP
+solver; rows_maximin_host is the numpy contract
+
 plus xmin._get_panel_not_in_portfolio_if_possible (XMIN's LEGACY caller,
 xmin.py:464-474) on the device.
 """
@@ -63,6 +68,8 @@ from .stats import (PanelComparison, PortfolioOverlap, compare_panel_distributio
 from .analysis import legacy_initial_committees, legacy_price  # noqa: F401
 from .stats import (PanelPrice, rows_first_holder_host, rows_mw_cover_host, rows_price_host,  # noqa: F401
                     rows_score_host)
+from .analysis import legacy_maximin  # noqa: F401
+from .stats import MaximinState, PanelMaximin, rows_maximin_host  # noqa: F401
 from . import _native, xmin  # noqa: F401
 
 __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_cats",
@@ -76,4 +83,5 @@ __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_c
            "legacy_panel_comparison", "legacy_portfolio_overlap", "PanelComparison", "PortfolioOverlap",
            "compare_panel_distributions", "portfolio_overlap", "rows_join_host", "rows_find_host",
            "legacy_initial_committees", "legacy_price", "PanelPrice", "rows_score_host", "rows_price_host",
-           "rows_mw_cover_host", "rows_first_holder_host"]
+           "rows_mw_cover_host", "rows_first_holder_host", "legacy_maximin", "PanelMaximin", "MaximinState",
+           "rows_maximin_host"]

@@ -40,6 +40,7 @@ CSA_PORTFOLIO_ACCUMULATE = 0x1  # csa_portfolio_pairs_async: add onto the stored
 CSA_GROUP_WHIST_ACCUMULATE = 0x1  # csa_group_whist_async: add onto the stored table
 CSA_PRICE_ACCUMULATE = 0x1  # csa_rows_price_async: the stored best yields only to a strictly greater score
 CSA_PRICE_NONE = 0xFFFFFFFFFFFFFFFF  # d_best[0] of an empty table
+CSA_MAXIMIN_START = 0x1  # csa_rows_maximin_async: initialise the state before the rounds
 
 # every symbol include/csa_legacy.h declares, with its ctypes signature
 _P = ctypes.c_void_p
@@ -123,6 +124,9 @@ SIGNATURES = {
     "csa_rows_price_async": (ctypes.c_int, [_P, _P, _U64, _I32, _I32, _P, _U64, _U32, _P, _P, _P, _U64, _P]),
     "csa_rows_mw_cover_async": (ctypes.c_int, [_P, _P, _U64, _I32, _I32, _U32, _P, _P, _P, _P, _P, _U64, _P]),
     "csa_rows_first_holder_async": (ctypes.c_int, [_P, _P, _U64, _I32, _I32, _P, _P]),
+    "csa_rows_maximin_scratch_bytes": (_U64, [_U64, _I32]),
+    "csa_rows_maximin_async": (ctypes.c_int, [_P, _P, _U64, _I32, _I32, _U32, ctypes.c_double, _U32, _U32, _P, _P, _P,
+                                              _P, _P, _P, _P, _U64, _P]),
 }
 
 _lib = None

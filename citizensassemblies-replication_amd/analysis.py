@@ -965,6 +965,19 @@ def legacy_initial_committees(instance: Instance, iterations: int, random_seed: 
     return legacy_panel_distribution(instance, iterations, random_seed, rng=rng)[3].initial_committees(rounds)
 
 
+def legacy_maximin(instance: Instance, iterations: int, random_seed: int, rounds: int = None, *, shrink: float = 0.8,
+                   resync: int = 16, rng: str = None):
+    """How fair could a lottery over exactly the panels a LEGACY run drew be made: ``legacy_panel_distribution(
+    instance, iterations, random_seed, rng=rng)`` followed by its ``maximin(rounds, shrink, resync)`` (``rounds``
+    defaults to 3 n; csa_rows_maximin_async over the run's sorted table on the device).  Returns a
+    ``stats.PanelMaximin``: a ``portfolio()`` that ``portfolio_probabilities``, ``portfolio_composition`` and
+    ``legacy_portfolio_overlap`` take, and ``lower <= z* <= upper`` for the optimum z* of the reference's first
+    leximin stage over the drawn panels (xmin.py:293-321) -- ``lower`` also bounds LEXIMIN's minimum selection
+    probability from below, and the portfolio is a warm start for a caller who has the solvers.  World size > 1
+    raises NotImplementedError, as ``legacy_panel_distribution``."""
+    return legacy_panel_distribution(instance, iterations, random_seed, rng=rng)[3].maximin(rounds, shrink, resync)
+
+
 def legacy_price(instance: Instance, weights, iterations: int, random_seed: int, chunk: int = 1 << 20):
     """Heuristic pricing over fresh draws that are not kept: among the panels [0, ``iterations``) of the LEGACY
     stream of ``random_seed``, the one with the largest weight sum.  Returns ``(frozenset of agent ids, value,

@@ -4024,3 +4024,94 @@ int csa_rows_first_holder_async(const uint64_t *d_rows, const uint64_t *d_len, u
 }
 
 }  // extern "C"
+
+// The maximin lottery over such a table (rows_maximin.inc) stands last, for the same reason.
+namespace {
+#include "rows_maximin.inc"
+}  // namespace
+
+extern "C" {
+
+uint64_t csa_rows_maximin_scratch_bytes(uint64_t cap, int32_t W) { return W < 1 ? 0 : rm_scratch_bytes(cap, W); }
+
+int csa_rows_maximin_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                           uint32_t rounds, double shrink, uint32_t resync, uint32_t flags, double *d_weights,
+                           double *d_scores, uint32_t *d_cover, uint32_t *d_row_count, uint64_t *d_state,
+                           uint32_t *d_picks, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+    if (int rc = rp_check("rows maximin", d_rows, d_len, cap, W, n)) return rc;
+    if (rm_update_lds(W) > 160 * 1024)
+        return fail(CSA_E_UNSUPPORTED, "rows maximin: W = %d needs %zu B of LDS", W, rm_update_lds(W));
+    if (!(shrink >= 0.5 && shrink < 1.0)) return fail(CSA_E_INVALID, "rows maximin: shrink = %g outside [0.5, 1)", shrink);
+    if (resync < 1 || resync > 64) return fail(CSA_E_INVALID, "rows maximin: resync = %u outside [1, 64]", resync);
+    if (flags & ~CSA_MAXIMIN_START) return fail(CSA_E_INVALID, "rows maximin: unknown flags 0x%x", flags);
+    if (!d_weights || !d_cover || !d_state || (cap && (!d_scores || !d_row_count)))
+        return fail(CSA_E_INVALID, "rows maximin: NULL weights, scores, cover, row counts or state");
+    const uint64_t need = rm_scratch_bytes(cap, W);
+    if (!d_scratch || scratch_bytes < need || ((uintptr_t)d_scratch & 7))
+        return fail(CSA_E_INVALID, "rows maximin: scratch_bytes < csa_rows_maximin_scratch_bytes, or scratch NULL or "
+                                   "not 8-byte aligned");
+    {
+        const void *buf[] = {d_weights, d_scores, d_cover, d_row_count, d_state, d_picks, d_scratch, d_rows, d_len};
+        const uint64_t bytes[] = {(uint64_t)n * 8, cap * 8, (uint64_t)n * 4, cap * 4, 32, (uint64_t)rounds * 4,
+                                  need, cap * (uint64_t)W * 8, 8};
+        for (int a = 0; a < 7; ++a)   // what is written, against everything after it
+            for (int b = a + 1; b < 9; ++b)
+                if (rs_overlap(buf[a], bytes[a], buf[b], bytes[b]))
+                    return fail(CSA_E_INVALID, "rows maximin: buffers %d and %d overlap", a, b);
+    }
+    const bool start = flags & CSA_MAXIMIN_START;
+    if (!start && rounds == 0) return CSA_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned long long *len = reinterpret_cast<const unsigned long long *>(d_len);
+    const uint64_t nb = rp_blocks(cap);
+    unsigned char *base = static_cast<unsigned char *>(d_scratch);
+    uint64_t *slab = reinterpret_cast<uint64_t *>(base);
+    double *delta = reinterpret_cast<double *>(base + 16 * nb);
+    uint32_t *first = reinterpret_cast<uint32_t *>(base + 16 * nb + (size_t)64 * W * 8);
+    uint64_t *pick_word = reinterpret_cast<uint64_t *>(base + 16 * nb + (size_t)64 * W * 12);
+    double *sum_word = reinterpret_cast<double *>(pick_word + 1);
+    auto score_pass = [&] {
+        if (nb)
+            hipLaunchKernelGGL(rp_score_kernel<>, dim3((unsigned)nb), dim3(kRpThreads), rp_score_lds(W), st, d_rows, len,
+                               cap, (int)W, (int)n, (const double *)d_weights, d_scores, slab);
+    };
+    auto bound = [&](int at_start) {
+        hipLaunchKernelGGL(rm_bound_kernel<>, dim3(1), dim3(kRpThreads), kRpBestLds, st, (const uint64_t *)slab, nb,
+                           (const double *)sum_word, at_start, d_state);
+    };
+    if (start) {
+        HIPCHK(hipMemsetAsync(first, 0xFF, (size_t)64 * W * 4, st));
+        if (cap) {
+            HIPCHK(hipMemsetAsync(d_row_count, 0, (size_t)cap * 4, st));
+            const uint64_t words = cap * (uint64_t)W;
+            const unsigned grid =
+                (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((words + 8 * kRpThreads - 1) / (8 * kRpThreads), 2048));
+            hipLaunchKernelGGL(rp_first_holder_kernel<>, dim3(grid), dim3(kRpThreads), (size_t)64 * W * 4, st, d_rows, len,
+                               cap, (int)W, (int)n, first);
+        }
+        hipLaunchKernelGGL(rm_start_kernel<>, dim3(1), dim3(kRpThreads), rm_pick_lds(W), st, (const uint32_t *)first,
+                           (int)W, (int)n, d_weights, d_cover, d_state, sum_word);
+        score_pass();
+        bound(1);
+    } else if (nb) {
+        hipLaunchKernelGGL(rm_rescan_kernel<>, dim3((unsigned)nb), dim3(kRpThreads), kRpBestLds, st, len, cap,
+                           (const double *)d_scores, slab);
+    }
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const int fresh = (r + 1) % resync == 0 || r == rounds - 1;
+        hipLaunchKernelGGL(rm_pick_kernel<>, dim3(1), dim3(kRpThreads), rm_pick_lds(W), st, d_rows, (int)W, (int)n,
+                           (const uint64_t *)slab, nb, shrink, fresh, d_weights, d_cover, d_row_count, d_state, d_picks, r,
+                           delta, pick_word, sum_word);
+        if (fresh) {
+            score_pass();
+            bound(0);
+        } else if (nb) {
+            hipLaunchKernelGGL(rm_update_kernel<>, dim3((unsigned)nb), dim3(kRpThreads), rm_update_lds(W), st, d_rows, len,
+                               cap, (int)W, (const double *)delta, (const uint64_t *)pick_word, d_scores, slab);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+}  // extern "C"

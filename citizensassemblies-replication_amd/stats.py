@@ -807,6 +807,41 @@ class PanelDistribution:
             picked, holders = _rows_at(t, picks, False), _rows_at(t, first, False)
         return committees_from_cover(picks, first, picked, holders, n, list(self._ids))
 
+    def maximin(self, rounds=None, shrink=0.8, resync=16):
+        """How fair could a lottery over exactly the panels this run drew be made?  The reference's
+        _dual_leximin_stage with no fixed probabilities and P ranging over the drawn panels (xmin.py:293-321) --
+        maximise the least selection probability of the agents some drawn panel holds -- solved as a zero-sum
+        game by ``rounds`` (default 3 n, as ``initial_committees``) multiplicative-weights rounds over the
+        sorted table: on its device csa_rows_maximin_async (plain launches, scores updated incrementally over
+        each row's intersection with the pick and summed afresh every ``resync`` rounds, one host wait at the
+        end), on the host ``rows_maximin_host``.  Returns a ``PanelMaximin``: the lottery of the picks as a
+        portfolio, each agent's exact selection probability under it, and ``lower <= optimum <= upper``.  No LP
+        solver is involved.  An empty run gives an empty result without a call; ValueError for rounds < 0,
+        ``shrink`` outside [0.5, 1) or ``resync`` outside [1, 64]."""
+        n = self._n
+        rounds = 3 * n if rounds is None else int(rounds)
+        n, rounds, shrink, resync = _maximin_arguments(n, self._W, rounds, shrink, resync)
+        ids = list(self._ids)
+        if not self.distinct:
+            none = np.zeros(n, np.int64)
+            return PanelMaximin(none[:0], none[:0].reshape(0, self._W), none, none, np.inf, n, ids)
+        t = self.table()
+        ops, device = _table_ops(t)
+        if device:
+            import torch
+            with torch.cuda.stream(ops.stream):
+                picks, b = ops.maximin(t, n, rounds, shrink, resync)
+                h = torch.cat([b.block, b.weights.view(torch.int64), b.cover.to(torch.int64) & 0xFFFFFFFF,
+                               picks.to(torch.int64) & 0xFFFFFFFF, _rows_at(t, picks, True).reshape(-1)]).cpu().numpy()
+            upper = float(h[0:1].view(np.float64)[0])
+            covered, cover = h[4:4 + n].view(np.float64) != 0.0, h[4 + n:4 + 2 * n]
+            picks, picked = h[4 + 2 * n:4 + 2 * n + rounds], h[4 + 2 * n + rounds:].reshape(rounds, t.W)
+        else:
+            picks, st = ops.maximin(t, n, rounds, shrink, resync)
+            upper, covered, cover = st.upper, st.weights != 0.0, st.cover
+            picked = _rows_at(t, picks, False)
+        return PanelMaximin(picks, picked, cover, covered, upper, n, ids)
+
     def __getstate__(self):
         f, m = self.multiplicities()
         rows = self._panel_rows(np.arange(self.distinct)) if self._panels is not None else None
@@ -1096,6 +1131,10 @@ class HostRowTables:
     def first_holder(self, table, n):
         return rows_first_holder_host(self._valid(table), n)
 
+    def maximin(self, table, n, rounds, shrink=0.8, resync=16, state=None):
+        """rows_maximin_host over the table's first ``length`` rows: ``(picks int64[rounds], MaximinState)``."""
+        return rows_maximin_host(self._valid(table), n, rounds, shrink, resync, state)
+
     def read(self, table, lists, draw_status=None):
         d = min(int(table.length[0]), table.cap)
         words = np.concatenate([np.zeros(4, np.uint32) if draw_status is None else np.asarray(draw_status, np.uint32),
@@ -1191,6 +1230,10 @@ class DeviceRowTables:
 
     def first_holder(self, table, n):
         return rows_first_holder_device(table, n, self.stream)
+
+    def maximin(self, table, n, rounds, shrink=0.8, resync=16, state=None):
+        """rows_maximin_device on this stream: ``(picks, MaximinBuffers)``, nothing waits."""
+        return rows_maximin_device(table, n, rounds, shrink, resync, state, self.stream)
 
     def read(self, table, lists, draw_status=None):
         """The one host wait: [draw status | table status | length], then the D rows (and lists)."""
@@ -1531,6 +1574,184 @@ def rows_first_holder_device(table, n, stream):
     N.check(N.lib().csa_rows_first_holder_async(N.ptr(table.rows), N.ptr(table.length), table.cap, table.W, int(n),
                                                 N.ptr(out), ctypes.c_void_p(stream.cuda_stream)))
     return out
+
+
+# --- the maximin lottery over a table (csrc/rows_maximin.inc) -------------------------------------------------
+# The reference's _dual_leximin_stage with no fixed probabilities and P ranging over drawn panels
+# (xmin.py:293-321), as a zero-sum game solved by multiplicative weights: a lower bound (the lottery of the
+# picks) and an upper bound (the weights as a dual point) on the optimum, no LP solver.  ``rows_maximin_host``
+# is csa_rows_maximin_async's contract in numpy, bit for bit.
+
+MaximinState = namedtuple("MaximinState", "weights scores cover row_count upper rounds best_row ratio")
+MaximinState.__doc__ = """What csa_rows_maximin_async keeps between calls, on the host: ``weights`` float64[n],
+``scores`` float64[D], ``cover`` int64[n], ``row_count`` int64[D], and the state block's four words -- ``upper``
+(float), ``rounds`` done, ``best_row`` of the last fresh pass (PRICE_NONE for an empty table) and its ``ratio``
+u."""
+
+MaximinBuffers = namedtuple("MaximinBuffers", "weights scores cover row_count block")
+MaximinBuffers.__doc__ = """The same state as device tensors: float64[n], float64[cap], int32[n] and int32[cap]
+(uint32 words), int64[4] (the state block: bits of upper, rounds done, best row, bits of u)."""
+
+
+def _maximin_arguments(n, W, rounds, shrink, resync):
+    n, rounds, shrink, resync = int(n), int(rounds), float(shrink), int(resync)
+    if not 0 < n <= 64 * W:
+        raise ValueError("n = %d agents do not fit rows of %d words" % (n, W))
+    if rounds < 0:
+        raise ValueError("rounds must not be negative")
+    if not 0.5 <= shrink < 1.0:
+        raise ValueError("shrink = %r outside [0.5, 1)" % (shrink,))
+    if not 1 <= resync <= 64:
+        raise ValueError("resync = %d outside [1, 64]" % resync)
+    return n, rounds, shrink, resync
+
+
+def rows_maximin_host(rows, n, rounds, shrink=0.8, resync=16, state=None):
+    """csa_rows_maximin_async's contract: ``(picks int64[rounds], MaximinState)``.  ``state=None`` starts
+    (CSA_MAXIMIN_START): unit weights on the agents some row holds, +0.0 elsewhere, a score pass, ``upper`` = the
+    best score / the lane-strided weight sum; a MaximinState continues it (the input is left unchanged).  Round r
+    (0-based within the call): the first best row p of the scores is picked and counted, its members are
+    covered once more and their weights become ``w * shrink`` with ``delta = w - w * shrink``; then, on a round
+    that is not fresh, every row's score loses the sum of ``delta`` over its intersection with row p (ascending
+    agent index from +0.0); on a fresh round -- ``(r + 1) % resync == 0`` or the call's last -- the weights are
+    scaled by n / (their lane-strided sum), the scores are summed afresh, and ``upper`` falls to the best score /
+    the new weights' sum when that is less.  An empty table picks NO_ROW and changes nothing."""
+    p = np.ascontiguousarray(rows, np.uint64)
+    if p.ndim != 2:
+        raise ValueError("rows must be uint64[D, W]")
+    D, W = p.shape
+    n, rounds, shrink, resync = _maximin_arguments(n, W, rounds, shrink, resync)
+    shrink = np.float64(shrink)
+    cols = _member_columns(p, n)
+    if state is None:
+        w = np.where(cols.any(axis=1), 1.0, 0.0).astype(np.float64)
+        cover, row_count, done = np.zeros(n, np.int64), np.zeros(D, np.int64), 0
+        sc = _score_columns(cols, w)
+        best_row, value = _best_of(sc)
+        with np.errstate(all="ignore"):
+            ratio = np.float64(np.inf) if best_row == PRICE_NONE else np.float64(value) / weights_sum_host(w, W)
+        upper = ratio
+    else:
+        w, sc = np.array(state.weights, np.float64).reshape(-1), np.array(state.scores, np.float64).reshape(-1)
+        cover, row_count = np.array(state.cover, np.int64).reshape(-1), np.array(state.row_count, np.int64).reshape(-1)
+        if len(w) != n or len(cover) != n or len(sc) != D or len(row_count) != D:
+            raise ValueError("the state is another table's")
+        upper, done, best_row, ratio = np.float64(state.upper), int(state.rounds), int(state.best_row), np.float64(state.ratio)
+    picks = np.full(rounds, NO_ROW, np.int64)
+    with np.errstate(all="ignore"):
+        for r in range(rounds if D else 0):
+            at, _ = _best_of(sc)
+            picks[r] = at
+            row_count[at] += 1
+            member = cols[:, at]
+            cover[member] += 1
+            done += 1
+            v = w * shrink
+            delta = np.where(member, w - v, 0.0)
+            w = np.where(member, v, w)
+            if (r + 1) % resync and r != rounds - 1:
+                t = np.zeros(D, np.float64)
+                for i in np.flatnonzero(member):
+                    np.add(t, delta[i], out=t, where=cols[i])
+                sc = sc - t
+                continue
+            w = w * (np.float64(n) / weights_sum_host(w, W))
+            sc = _score_columns(cols, w)
+            best_row, value = _best_of(sc)
+            ratio = np.float64(value) / weights_sum_host(w, W)
+            if ratio < upper:
+                upper = ratio
+    return picks, MaximinState(w, sc, cover, row_count, float(upper), done, best_row, float(ratio))
+
+
+def rows_maximin_device(table, n, rounds, shrink=0.8, resync=16, state=None, stream=None):
+    """Enqueue csa_rows_maximin_async over RowTable ``table`` on ``stream`` (default: the current stream of the
+    table's device); nothing waits.  ``state=None`` starts on fresh buffers (CSA_MAXIMIN_START); a
+    MaximinBuffers is continued in place.  Returns ``(picks, buffers)``: int32 of ``rounds`` uint32 words, and
+    the MaximinBuffers.  Bad arguments raise ValueError here or CsaError from the library, before any launch."""
+    import torch
+    L = N.lib()
+    dev = table.length.device
+    n, rounds, shrink, resync = _maximin_arguments(n, table.W, rounds, shrink, resync)
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(stream):
+        need = int(L.csa_rows_maximin_scratch_bytes(table.cap, table.W))
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        picks = torch.empty(max(rounds, 1), dtype=torch.int32, device=dev)
+        flags = 0
+        if state is None:
+            flags = N.CSA_MAXIMIN_START
+            state = MaximinBuffers(torch.empty(n, dtype=torch.float64, device=dev),
+                                   torch.empty(max(table.cap, 1), dtype=torch.float64, device=dev),
+                                   torch.empty(n, dtype=torch.int32, device=dev),
+                                   torch.empty(max(table.cap, 1), dtype=torch.int32, device=dev),
+                                   torch.empty(4, dtype=torch.int64, device=dev))
+    N.check(L.csa_rows_maximin_async(N.ptr(table.rows), N.ptr(table.length), table.cap, table.W, n, rounds, shrink,
+                                     resync, flags, N.ptr(state.weights), N.ptr(state.scores), N.ptr(state.cover),
+                                     N.ptr(state.row_count), N.ptr(state.block), N.ptr(picks), N.ptr(scratch), need,
+                                     ctypes.c_void_p(stream.cuda_stream)))
+    return picks[:rounds], state
+
+
+def maximin_buffers_host(buffers, length):
+    """A MaximinBuffers copied to the host as the MaximinState of a table of ``length`` rows (this waits)."""
+    d = int(length)
+    block = buffers.block.cpu().numpy().view(np.uint64)
+    return MaximinState(buffers.weights.cpu().numpy(), buffers.scores[:d].cpu().numpy(),
+                        buffers.cover.cpu().numpy().astype(np.int64) & 0xFFFFFFFF,
+                        buffers.row_count[:d].cpu().numpy().astype(np.int64) & 0xFFFFFFFF,
+                        float(block[0:1].view(np.float64)[0]), int(block[1]), int(block[2]),
+                        float(block[3:4].view(np.float64)[0]))
+
+
+class PanelMaximin:
+    """The maximin lottery over a run's distinct panels after ``rounds`` multiplicative-weights rounds.
+
+    ``panels``: the distinct picked panels (frozensets of agent ids) in ascending row order; ``rows``: their rows
+    in the run's sorted table; ``counts``: how often each was picked (integers summing to ``rounds``);
+    ``probabilities`` = counts / rounds.  ``alloc``: agent id -> ``Fraction(cover, rounds)``, the agent's exact
+    selection probability under that lottery.  ``covered_agents``: the agents some drawn panel holds.
+    ``lower``: a Fraction, the minimum of ``alloc`` over ``covered_agents`` -- a lower bound on the optimum of
+    the maximin LP over the drawn panels, hence on LEXIMIN's minimum probability.  ``upper``: float, the least
+    (best score / weight sum) over the fresh passes, an upper bound on the same optimum.  ``output_lines`` names
+    the agents no drawn panel contains.  No rounds (or an empty run): no panels, ``lower`` = 0."""
+
+    def __init__(self, picks, picked_rows, cover, covered, upper, n, agent_ids):
+        from fractions import Fraction
+        from .instance import unpack_panel
+        ids = list(agent_ids)
+        picks = [int(x) for x in np.asarray(picks, np.int64).tolist()]
+        at = {}
+        for r, p in enumerate(picks):
+            if p != NO_ROW:
+                at.setdefault(p, []).append(r)
+        self.rows = sorted(at)
+        self.counts = [len(at[p]) for p in self.rows]
+        self.rounds = sum(self.counts)
+        self.panels = [frozenset(ids[q] for q in unpack_panel(np.ascontiguousarray(picked_rows[at[p][0]]).view(np.uint64), n))
+                       for p in self.rows]
+        self.probabilities = [c / self.rounds for c in self.counts]
+        cover = [int(x) for x in np.asarray(cover, np.int64).tolist()]
+        self.alloc = {aid: Fraction(cover[i], self.rounds) if self.rounds else Fraction(0) for i, aid in enumerate(ids)}
+        self.covered_agents = frozenset(ids[i] for i in range(n) if covered[i])
+        self.lower = min((self.alloc[a] for a in self.covered_agents), default=Fraction(0))
+        self.upper = float(upper)
+        self.output_lines = ["Agent %s not contained in any drawn panel." % (aid,) for i, aid in enumerate(ids)
+                             if not covered[i]]
+        if len(self.covered_agents) == len(ids):
+            self.output_lines.append("All agents are contained in some drawn panel.")
+
+    def portfolio(self):
+        """``(panels, probabilities)`` as ``portfolio_probabilities``, ``portfolio_composition`` and
+        ``legacy_portfolio_overlap`` take them."""
+        return list(self.panels), list(self.probabilities)
+
+    def __eq__(self, other):
+        return isinstance(other, PanelMaximin) and self.__dict__ == other.__dict__
+
+    def __repr__(self):
+        return "PanelMaximin(%d panels, %d rounds, lower=%s, upper=%r)" % (len(self.panels), self.rounds, self.lower,
+                                                                          self.upper)
 
 
 PanelPrice = namedtuple("PanelPrice", "panel value row first multiplicity")

@@ -606,6 +606,59 @@ int csa_rows_mw_cover_async(const uint64_t *d_rows, const uint64_t *d_len, uint6
 int csa_rows_first_holder_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
                                 uint32_t *d_first_row, void *stream);
 
+/* The maximin lottery over a table of drawn panels: the reference's _dual_leximin_stage with no fixed
+ * probabilities and P ranging over the table's rows (xmin.py:293-321, the first outer iteration of
+ * _expand_distribution_leximin) --
+ *     maximise z  s.t.  sum over the rows P holding i of x_P >= z for every agent i some row holds,
+ *                       sum of x_P = 1,  x >= 0
+ * -- solved as a zero-sum game by the multiplicative-weights loop, no LP solver.  After T rounds x = (how often
+ * each row was picked) / T is a lottery over the rows under which agent i is selected with probability
+ * d_cover[i] / T exactly, so the least of these over the agents some row holds is a LOWER bound on the optimum
+ * z* (and on LEXIMIN's minimum probability: the drawn panels are some of the feasible ones); every weight
+ * vector w met is a dual point, so z* <= the best score / the sum of w, the UPPER bound.  Stream-ordered; the
+ * length is read on the device; nothing waits, nothing is allocated.
+ *
+ * Table, n, score, "best" (float64 values compared with >, ties to the lowest row) and the lane-strided sum
+ * are the pricing entry points' above.  State, all caller-owned, read and written, so a second call continues
+ * the first: d_weights float64[n]; d_scores float64[cap]; d_cover uint32[n]; d_row_count uint32[cap];
+ * d_state uint64[4] = (bits of `upper`, rounds done, row of the last fresh best, bits of the last fresh ratio
+ * u); d_picks uint32[rounds] or NULL.
+ *
+ * Start (CSA_MAXIMIN_START in flags): w[i] = 1.0 where some valid row holds agent i, else +0.0 (the
+ * first-holder pass); cover, row_count, rounds done = 0; a fresh score pass over w writes the scores; U = the
+ * best score, s = the lane-strided sum of w, upper = U / s (IEEE division); the state's row and u are that
+ * pass's.  An empty table starts as (+inf, 0, CSA_PRICE_NONE, +inf) with all weights +0.0.
+ *
+ * Round r of a call (0-based) is FRESH when (r + 1) % resync == 0 or r == rounds - 1, so every call ends on
+ * fresh scores and normalised weights.
+ *   1. p = the first row holding the maximum of d_scores.
+ *   2. d_picks[r] = p; d_row_count[p] += 1; d_cover[i] += 1 for the members of row p; rounds done += 1.
+ *   3. For the members of row p: v = w[i] * shrink (one rounded multiply), delta[i] = w[i] - v (one rounded
+ *      subtract, never an fma), w[i] = v.  For everyone else delta[i] = +0.0.
+ *   4. Not fresh: for every valid row d, t = the sum of delta[i] over the set bits i of row_d & row_p in
+ *      ascending i from +0.0, one rounded add each; d_scores[d] = d_scores[d] - t.
+ *   5. Fresh: s = the lane-strided sum of w; f = (double)n / s; w[i] = w[i] * f for all i; a fresh score pass
+ *      writes the scores; U = its best; s2 = the lane-strided sum of the new w; u = U / s2; upper = u if
+ *      u < upper; u and the best row are recorded in the state.
+ * An empty table writes 0xFFFFFFFF picks and changes nothing else.  rounds == 0 with CSA_MAXIMIN_START only
+ * initialises; without it nothing is launched.  Launches: two per round, three on a fresh round, plain
+ * launches on the caller's stream with no host wait between them; a call without CSA_MAXIMIN_START first
+ * rebuilds its per-tile bests from d_scores, so the scratch need not survive between calls.
+ * d_scratch: csa_rows_maximin_scratch_bytes(cap, W) bytes, 8-byte aligned (the per-tile bests, delta, the
+ * first holders, two words).
+ *
+ * CSA_E_UNSUPPORTED for cap >= 2^32 - 1 or a W beyond the LDS.  CSA_E_INVALID, before any device call, for
+ * what the pricing entry points refuse of the table and n, shrink outside [0.5, 1), resync outside [1, 64] (so
+ * the weights between fresh rounds cannot underflow), unknown flags, a NULL d_weights / d_cover / d_state, a
+ * NULL d_scores / d_row_count with cap > 0, state buffers that overlap each other, the table, the length or
+ * the scratch, or a scratch that is NULL, short or misaligned. */
+#define CSA_MAXIMIN_START 0x1u
+uint64_t csa_rows_maximin_scratch_bytes(uint64_t cap, int32_t W);
+int csa_rows_maximin_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                           uint32_t rounds, double shrink, uint32_t resync, uint32_t flags, double *d_weights,
+                           double *d_scores, uint32_t *d_cover, uint32_t *d_row_count, uint64_t *d_state,
+                           uint32_t *d_picks /* or NULL */, void *d_scratch, uint64_t scratch_bytes, void *stream);
+
 /* Multi-GPU pair exchange: pack the upper triangle incl. the diagonal of the
  * n*n int64 pair counts row-major into n(n+1)/2 int32 (every count must be
  * < 2^31), and unpack it back (overwriting the upper triangle). */
