@@ -29,6 +29,8 @@ def lib():
         L.oracle_draw.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P, P, ctypes.c_int,
                                   ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                   P, P, P, P, ctypes.c_int]
+        L.oracle_draw_addr.restype = ctypes.c_int
+        L.oracle_draw_addr.argtypes = L.oracle_draw.argtypes + [P, P]
         L.oracle_counts.restype = None
         L.oracle_counts.argtypes = [P, ctypes.c_uint64, ctypes.c_int, P]
         L.oracle_pairs.restype = None
@@ -60,19 +62,28 @@ def arrays(inst: OracleInstance):
 
 
 def draw(inst, k, seed, panel_begin, n_panels, max_attempts=1 << 20, want_picks=False, threads=None,
-         rejects=None):
+         rejects=None, addr_next=None, ring_tally=None):
     """Returns (status, panels uint64[S,W], attempts uint32[S], picks int32[S,k] or None).
     ``rejects`` (uint32[S], optional) receives each panel's min-quota rejections; the other
-    attempts - 1 restarts are SelectionErrors."""
+    attempts - 1 restarts are SelectionErrors.  ``addr_next`` (int32[n], optional): same-address
+    rings (check_same_address); ``ring_tally`` (uint64[2], optional) then receives the call's attempts
+    that failed inside a same-address deletion and its same-address deletions in another 64-person
+    word than their pick's."""
     pf, fmin, fmax, fcat = arrays(inst)
     W = (inst.n + 63) // 64
     panels = np.zeros((n_panels, W), np.uint64)
     attempts = np.zeros(n_panels, np.uint32)
     picks = np.full((n_panels, k), -1, np.int32) if want_picks else None
     threads = threads or os.cpu_count() or 1
-    rc = lib().oracle_draw(inst.n, inst.C, inst.F, _ptr(pf), _ptr(fmin), _ptr(fmax), _ptr(fcat), k,
-                           seed, panel_begin, n_panels, max_attempts, _ptr(panels), _ptr(picks),
-                           _ptr(attempts), _ptr(rejects), threads)
+    args = (inst.n, inst.C, inst.F, _ptr(pf), _ptr(fmin), _ptr(fmax), _ptr(fcat), k, seed, panel_begin, n_panels,
+            max_attempts, _ptr(panels), _ptr(picks), _ptr(attempts), _ptr(rejects), threads)
+    if addr_next is None and ring_tally is None:
+        rc = lib().oracle_draw(*args)
+    else:
+        ring = None if addr_next is None else np.ascontiguousarray(addr_next, np.int32)
+        assert ring is None or ring.shape == (inst.n,)
+        assert ring_tally is None or (ring_tally.dtype == np.uint64 and ring_tally.size >= 2)
+        rc = lib().oracle_draw_addr(*args, _ptr(ring), _ptr(ring_tally))
     return rc, panels, attempts, picks
 
 

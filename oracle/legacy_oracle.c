@@ -8,7 +8,9 @@
  *   find_max_ratio_cat        legacy.py:124-157   strict '>' argmax from -100.0,
  *                                                 exact integer cross-multiplication
  *   holder scan               legacy.py:186-197   r-th remaining holder, ascending id
- *   delete_person             legacy.py:103-120   sel+=1 / rem-=1 on the picked row
+ *   delete_person             legacy.py:103-120   sel+=1 / rem-=1 on the picked row; with same-address
+ *                                                 rings (oracle_draw_addr) the pick's household,
+ *                                                 legacy.py:78-99, 109-113, person by person
  *   delete_all_in_cat         legacy.py:47-62     bulk cascade over full features
  *   find_random_sample_legacy legacy.py:178-200   k steps + empty-pool SelectionError
  *   check_min_cats            legacy.py:160-168
@@ -18,7 +20,8 @@
  * attempt, panel), word step&3; r = 1 + ((word*rem) >> 32)).
  *
  * Pinned by tests/test_oracle_golden.py against tests/golden/philox_*.json,
- * which tools/make_goldens.py produced by driving the unmodified reference.
+ * which tools/make_goldens.py produced by driving the unmodified reference; the same-address rings by
+ * tests/test_oracle_address.py against tests/golden/address_*.json and cell_address_*.json.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -56,10 +59,13 @@ typedef struct {
     int32_t *pool;        /* F */
 } oinst;
 
-/* one attempt; returns 0 accepted, 1 SelectionError, 2 min-quota rejection, -1 no candidate */
+/* one attempt; returns 0 accepted, 1 SelectionError, 2 min-quota rejection, -1 no candidate.
+ * addr (or NULL): same-address rings; tally (with addr): [0] += 1 where a same-address deletion
+ * (selected=False, legacy.py:113) raised the SelectionError, [1] += same-address deletions in another
+ * 64-person word than their pick's */
 static int attempt_once(const oinst *I, int k, uint64_t seed, uint64_t panel, uint32_t attempt,
                         uint64_t *remaining, int32_t *sel, int32_t *rem, uint64_t *picked,
-                        uint64_t *del, int32_t *picks) {
+                        uint64_t *del, int32_t *picks, const int32_t *addr, uint64_t *tally) {
     const int F = I->F, W = I->W, n = I->n, C = I->C;
     memset(sel, 0, sizeof(int32_t) * F);
     memcpy(rem, I->pool, sizeof(int32_t) * F);
@@ -114,6 +120,25 @@ static int attempt_once(const oinst *I, int k, uint64_t seed, uint64_t panel, ui
                     int g = row[c];
                     sel[g] += 1;
                     rem[g] -= 1;
+                    /* legacy.py:73; without rings the test after the cascades covers it */
+                    if (addr && rem[g] == 0 && sel[g] < I->fmin[g]) return 1;
+                }
+                if (addr) {
+                    /* legacy.py:109-113: every remaining agent of the pick's ring, selected=False,
+                     * one feature at a time, before the cascades */
+                    int q = addr[p];
+                    for (int guard = 0; q != p && guard < n; q = addr[q], ++guard) {
+                        const uint64_t qb = 1ull << (q & 63);
+                        if (!(remaining[q >> 6] & qb)) continue;
+                        remaining[q >> 6] &= ~qb;
+                        tally[1] += (q >> 6) != (p >> 6);
+                        const int32_t *qrow = I->pf + (size_t)q * C;
+                        for (int c = 0; c < C; ++c) {
+                            int g = qrow[c];
+                            rem[g] -= 1;
+                            if (rem[g] == 0 && sel[g] < I->fmin[g]) { tally[0] += 1; return 1; }
+                        }
+                    }
                 }
                 for (int c = 0; c < C; ++c) {
                     int g = row[c];
@@ -147,11 +172,19 @@ static int attempt_once(const oinst *I, int k, uint64_t seed, uint64_t panel, ui
     return 0;
 }
 
-int oracle_draw(int n, int C, int F, const int32_t *pf, const int32_t *fmin, const int32_t *fmax,
-                const int32_t *fcat, int k, uint64_t seed, uint64_t panel_begin, uint64_t n_panels,
-                uint32_t max_attempts, uint64_t *panels_out, int32_t *picks_out, uint32_t *attempts_out,
-                uint32_t *rejects_out, int nthreads) {
+/* oracle_draw with check_same_address: addr_next[p] (or NULL: no rings) is the next agent at p's
+ * address, each address's agents closed into a ring.  ring_tally (2 words, or NULL) receives the call's
+ * totals: [0] attempts that failed inside a same-address deletion, [1] same-address deletions in
+ * another word than their pick's. */
+int oracle_draw_addr(int n, int C, int F, const int32_t *pf, const int32_t *fmin, const int32_t *fmax,
+                     const int32_t *fcat, int k, uint64_t seed, uint64_t panel_begin, uint64_t n_panels,
+                     uint32_t max_attempts, uint64_t *panels_out, int32_t *picks_out, uint32_t *attempts_out,
+                     uint32_t *rejects_out, int nthreads, const int32_t *addr_next, uint64_t *ring_tally) {
     if (n <= 0 || C <= 0 || F <= 0 || k < 0 || !pf || !fmin || !fmax || !fcat) return OR_E_INVALID;
+    if (addr_next)
+        for (int p = 0; p < n; ++p)
+            if (addr_next[p] < 0 || addr_next[p] >= n) return OR_E_INVALID;
+    uint64_t tally0 = 0, tally1 = 0;
     oinst I;
     I.n = n; I.C = C; I.F = F; I.W = (n + 63) / 64;
     I.pf = pf; I.fmin = fmin; I.fmax = fmax; I.fcat = fcat;
@@ -174,6 +207,7 @@ int oracle_draw(int n, int C, int F, const int32_t *pf, const int32_t *fmin, con
         uint64_t *del = (uint64_t *)malloc(sizeof(uint64_t) * W);
         int32_t *sel = (int32_t *)malloc(sizeof(int32_t) * F);
         int32_t *rem = (int32_t *)malloc(sizeof(int32_t) * F);
+        uint64_t tally[2] = {0, 0};
 #pragma omp for schedule(dynamic, 16)
         for (int64_t i = 0; i < (int64_t)n_panels; ++i) {
             uint64_t panel = panel_begin + (uint64_t)i;
@@ -181,7 +215,7 @@ int oracle_draw(int n, int C, int F, const int32_t *pf, const int32_t *fmin, con
             uint32_t a = 0, rejects = 0;
             int rc = 1;
             for (; a < max_attempts; ++a) {
-                rc = attempt_once(&I, k, seed, panel, a, remaining, sel, rem, picked, del, picks);
+                rc = attempt_once(&I, k, seed, panel, a, remaining, sel, rem, picked, del, picks, addr_next, tally);
                 if (rc == 0 || rc < 0) break;
                 rejects += rc == 2;  /* check_min_cats failed: "Rejected" (analysis.py:155-159) */
             }
@@ -197,10 +231,23 @@ int oracle_draw(int n, int C, int F, const int32_t *pf, const int32_t *fmin, con
             if (rejects_out) rejects_out[i] = rejects;
         }
         free(remaining); free(picked); free(del); free(sel); free(rem);
+#pragma omp atomic
+        tally0 += tally[0];
+#pragma omp atomic
+        tally1 += tally[1];
     }
     free(I.featmask);
     free(I.pool);
+    if (ring_tally) { ring_tally[0] = tally0; ring_tally[1] = tally1; }
     return status;
+}
+
+int oracle_draw(int n, int C, int F, const int32_t *pf, const int32_t *fmin, const int32_t *fmax,
+                const int32_t *fcat, int k, uint64_t seed, uint64_t panel_begin, uint64_t n_panels,
+                uint32_t max_attempts, uint64_t *panels_out, int32_t *picks_out, uint32_t *attempts_out,
+                uint32_t *rejects_out, int nthreads) {
+    return oracle_draw_addr(n, C, F, pf, fmin, fmax, fcat, k, seed, panel_begin, n_panels, max_attempts, panels_out,
+                            picks_out, attempts_out, rejects_out, nthreads, NULL, NULL);
 }
 
 /* per-person counts: counts[p] = number of panels containing p */

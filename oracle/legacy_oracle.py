@@ -11,7 +11,10 @@ What it restates (reference file:line):
                                                    randint on every improvement)
   * holder scan              legacy.py:186-197    (a6: r-th remaining holder in
                                                    ascending agent id)
-  * delete_person            legacy.py:103-120, 67-75 (a7)
+  * delete_person            legacy.py:103-120, 67-75 (a7; with check_same_address the
+                                                   pick's household, legacy.py:78-99,
+                                                   109-113, one person and one feature
+                                                   at a time)
   * delete_all_in_cat        legacy.py:47-62      (a8, bulk order-free form)
   * find_random_sample_legacy legacy.py:178-200   (k steps + empty-pool test)
   * check_min_cats           legacy.py:160-168    (a9)
@@ -116,10 +119,17 @@ def read_instance(cat_csv, resp_csv, k):
                           agent_ids=list(range(len(person_feat))))
 
 
-def draw_attempt(inst, k, rng, sel=None, rem=None, present=None):
+def draw_attempt(inst, k, rng, sel=None, rem=None, present=None, addr_next=None):
     """One call of find_random_sample_legacy (legacy.py:178-200) on array state.
 
     ``rng(step, rem_f)`` is invoked at every argmax improvement (legacy.py:149).
+    ``addr_next`` (check_same_address=True): ``addr_next[p]`` is the next agent at p's address, the
+    agents of one address closed into a ring (a lone agent points to itself).  After the pick
+    (really_delete_person, selected=True) every still-present member of its ring is deleted in ring
+    order with selected=False (legacy.py:109-113), feature by feature, and the attempt FAILs at the
+    first ``remaining == 0 and selected < min`` (legacy.py:73) -- before the cascades, as the
+    reference raises it.  (The reference walks the household in dict order, the ring from the pick
+    on: the same deletions, and both FAIL iff one of them empties a feature below its minimum.)
     Returns (status, picks, sel, rem, present); status OK or FAIL (SelectionError).
     Raises NoCandidateError where the reference raises KeyError (legacy.py:188).
     """
@@ -162,11 +172,33 @@ def draw_attempt(inst, k, rng, sel=None, rem=None, present=None):
                         break
             if pick is not None:
                 picks.append(pick)
-                # a7: really_delete_person(selected=True)
                 present[pick] = False
-                for g in pf[pick]:
-                    sel[g] += 1
-                    rem[g] -= 1
+                if addr_next is None:
+                    # a7: really_delete_person(selected=True); its legacy.py:73 test is the one
+                    # after the cascades (nothing between them raises or adds to rem)
+                    for g in pf[pick]:
+                        sel[g] += 1
+                        rem[g] -= 1
+                else:
+                    # a7 with check_same_address, in the reference's own order (legacy.py:107-113)
+                    for g in pf[pick]:
+                        sel[g] += 1
+                        rem[g] -= 1
+                        if rem[g] == 0 and sel[g] < fmin[g]:
+                            return FAIL, picks, sel, rem, present
+                    q = addr_next[pick]
+                    for _ in range(n):                  # a ring has at most n members
+                        if q == pick:
+                            break
+                        if present[q]:
+                            present[q] = False          # really_delete_person(selected=False)
+                            for g in pf[q]:
+                                rem[g] -= 1
+                                if rem[g] == 0 and sel[g] < fmin[g]:
+                                    return FAIL, picks, sel, rem, present
+                        q = addr_next[q]
+                    else:
+                        raise ValueError("addr_next does not lead back to agent %d" % pick)
                 # a8: cascade for the picked person's full features (bulk form)
                 full = [g for g in pf[pick] if sel[g] == fmax[g]]
                 if full:
@@ -217,11 +249,14 @@ class MtRng:
         return rng
 
 
-def legacy_find(inst, k, rng_src, panel, max_attempts=1 << 20):
-    """analysis.py:141-159.  Returns (picks in pick order, attempts used)."""
+def legacy_find(inst, k, rng_src, panel, max_attempts=1 << 20, sel=None, rem=None, present=None, addr_next=None):
+    """analysis.py:141-159.  Returns (picks in pick order, attempts used).  Every attempt starts from
+    (sel, rem, present) -- the default state where None -- with the same-address rings ``addr_next``."""
     attempt = 0
+    sel0, rem0, present0 = sel, rem, present
     while attempt < max_attempts:
-        status, picks, sel, _rem, _present = draw_attempt(inst, k, rng_src.for_attempt(panel, attempt))
+        status, picks, sel, _rem, _present = draw_attempt(inst, k, rng_src.for_attempt(panel, attempt),
+                                                          sel0, rem0, present0, addr_next)
         attempt += 1
         if status == FAIL:
             continue
@@ -243,7 +278,7 @@ class OracleResult:
         return len(set(self.panels))
 
 
-def legacy_probabilities(inst, S, seed, mode="philox", panel_begin=0, want_pairs=True):
+def legacy_probabilities(inst, S, seed, mode="philox", panel_begin=0, want_pairs=True, addr_next=None):
     """analysis.py:162-191 restated; returns raw integer results."""
     for c in range(inst.C):                       # analysis.py:174-176
         feats = [g for g in range(inst.F) if inst.fcat[g] == c]
@@ -255,7 +290,7 @@ def legacy_probabilities(inst, S, seed, mode="philox", panel_begin=0, want_pairs
     panels, picks_all, attempts = [], [], []
     X = np.zeros((S, n), np.float64) if want_pairs else None
     for i in range(S):
-        picks, att = legacy_find(inst, inst.k, src, panel_begin + i)
+        picks, att = legacy_find(inst, inst.k, src, panel_begin + i, addr_next=addr_next)
         panel = tuple(sorted(picks))
         panels.append(panel)
         picks_all.append(picks)

@@ -83,6 +83,8 @@ class PhiloxHarness:
 
     def __enter__(self):
         lg, an = self.legacy, self.analysis
+        an = an or types.SimpleNamespace(legacy_find=None, find_random_sample_legacy=None)   # legacy.py alone
+        self.analysis = an
         self.saved = (an.legacy_find, an.find_random_sample_legacy, lg.find_max_ratio_cat,
                       lg.random.randint)
         orig_find, orig_draw, orig_ratio, _ = self.saved
@@ -282,6 +284,69 @@ def address_case(legacy, analysis, case, inst_dir, k, S, seed, mode):
             "picks": picks if S * k <= 50000 else picks[:200], "single_attempts": single}
 
 
+# check_same_address on a synthetic pool too large for the CSV instances' kernel: the cell of
+# tests/test_gpu_draw_matrix.py that runs draw_kernel<64, 1, 2, true> (n = 4133, k = 20), with the
+# households of tests/address_cases.py as its address column.  The pool is not stored: the cell recipe
+# regenerates it, and the fixture carries a sha256 of person_feat.  (case, cell, panels, single records)
+ADDRESS_CELL_CASES = [
+    ("cell_address_g64_1_2", "draw_kernel<64, 1, 2, true>", 36, 12),
+]
+
+
+def address_cell_case(legacy, case, cell_name, S, n_single):
+    import copy
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import address_cases as AC
+    from test_gpu_draw_matrix import BEGIN, BY_NAME, SEED, oracle_instance, recipe_of
+    cell = BY_NAME[cell_name]
+    cats0, o = oracle_instance(recipe_of(cell))
+    n, k = o.n, cell.k
+    ring, label = AC.ring_of(n)
+    names = [(c, f) for c in cats0 for f in cats0[c]]
+    pool = o.pool_counts()
+    categories = {c: {f: {"min": v["min"], "max": v["max"], "selected": 0, "remaining": pool[names.index((c, f))]}
+                      for f, v in cats0[c].items()} for c in cats0}
+    agents = {i: {names[g][0]: names[g][1] for g in row} for i, row in enumerate(o.person_feat)}
+    columns_data = {i: {ADDR_COLS[0]: "household %d" % label[i], ADDR_COLS[1]: "Z"} for i in range(n)}
+    begin = BEGIN + 300 - S // 2          # panel 2^32 is row S / 2
+    picks, attempts, single = [], [], []
+    t0 = time.time()
+    with PhiloxHarness(legacy, None, SEED) as h:
+        for i in range(S):
+            a = -1
+            while True:
+                a += 1
+                cats, people = copy.deepcopy(categories), copy.deepcopy(agents)
+                h.panel, h.attempt, h.step = begin + i, a, 0
+                rec = {"panel": begin + i, "attempt": a}
+                try:
+                    sel, _ = legacy.find_random_sample_legacy(cats, people, columns_data, k, True, ADDR_COLS)
+                except legacy.SelectionError:
+                    if len(single) < n_single:
+                        single.append(dict(rec, status="SelectionError"))
+                    continue
+                ok, _ = legacy.check_min_cats(cats)
+                if len(single) < n_single:
+                    single.append(dict(rec, status="ok", picks=list(sel),
+                                       selected=[[c, f, v["selected"], v["remaining"]] for c in cats
+                                                 for f, v in cats[c].items()],
+                                       people_left_count=len(people),
+                                       people_left_sha256=sha(np.array(sorted(people), np.int32))))
+                if not ok:
+                    continue
+                picks.append(list(sel))
+                attempts.append(a + 1)
+                break
+    return {"case": case, "cell": cell_name, "k": k, "S": S, "seed": SEED, "n": n, "rng": "philox",
+            "panel_begin": begin,
+            "generator": "tools/make_goldens.py driving the unmodified reference's find_random_sample_legacy "
+                         "with check_same_address=True in a legacy_find-shaped restart loop, on the cell's "
+                         "regenerated pool with the households of tests/address_cases.py as address column",
+            "reference_seconds": round(time.time() - t0, 3),
+            "person_feat_sha256": sha(np.asarray(o.person_feat, np.int32)),
+            "ring": ring.tolist(), "picks": picks, "attempts": attempts, "single_attempts": single}
+
+
 def mt_goldens():
     out = {}
     for name, k, rel in (
@@ -329,6 +394,14 @@ def main(argv):
         print("%-28s philox unique=%d attempts=%d  mt unique=%d attempts=%d" % (
             case, g["philox"]["unique"], sum(g["philox"]["attempts"]), g["mt"]["unique"],
             sum(g["mt"]["attempts"])), file=sys.stderr)
+    for case, cell_name, S, n_single in ADDRESS_CELL_CASES:
+        if want and case not in want and "address" not in want:
+            continue
+        g = address_cell_case(legacy, case, cell_name, S, n_single)
+        with open(os.path.join(GOLD, "%s.json" % case), "w") as fh:
+            json.dump(g, fh, separators=(",", ":"))
+        print("%-28s n=%d attempts=%d  %.1fs" % (case, g["n"], sum(g["attempts"]), g["reference_seconds"]),
+              file=sys.stderr)
 
 
 if __name__ == "__main__":
