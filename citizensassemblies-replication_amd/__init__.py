@@ -70,6 +70,7 @@ from .stats import (PanelPrice, rows_first_holder_host, rows_mw_cover_host, rows
                     rows_score_host)
 from .analysis import legacy_maximin  # noqa: F401
 from .stats import MaximinState, PanelMaximin, rows_maximin_host  # noqa: F401
+from .stats import household_groups  # noqa: F401
 from . import _native, xmin  # noqa: F401
 
 __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_cats",
@@ -84,4 +85,4 @@ __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_c
            "compare_panel_distributions", "portfolio_overlap", "rows_join_host", "rows_find_host",
            "legacy_initial_committees", "legacy_price", "PanelPrice", "rows_score_host", "rows_price_host",
            "rows_mw_cover_host", "rows_first_holder_host", "legacy_maximin", "PanelMaximin", "MaximinState",
-           "rows_maximin_host"]
+           "rows_maximin_host", "household_groups"]

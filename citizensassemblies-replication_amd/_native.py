@@ -40,6 +40,8 @@ CSA_PORTFOLIO_ACCUMULATE = 0x1  # csa_portfolio_pairs_async: add onto the stored
 CSA_GROUP_WHIST_ACCUMULATE = 0x1  # csa_group_whist_async: add onto the stored table
 CSA_PRICE_ACCUMULATE = 0x1  # csa_rows_price_async: the stored best yields only to a strictly greater score
 CSA_PRICE_NONE = 0xFFFFFFFFFFFFFFFF  # d_best[0] of an empty table
+CSA_ADDRESS_GENERAL = 0  # csa_instance_set_address_route: every ring draw on draw_kernel<64, ..., true>
+CSA_ADDRESS_BATCH = 1    # batch draws of a register-kernel instance on the kernel's household form
 CSA_MAXIMIN_START = 0x1  # csa_rows_maximin_async: initialise the state before the rounds
 
 # every symbol include/csa_legacy.h declares, with its ctypes signature
@@ -99,6 +101,8 @@ SIGNATURES = {
     "csa_legacy_draw_mt": (ctypes.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _U64, _U32,
                                           _I32, _P, _P, _P, _P, _P, _P, _P]),
     "csa_instance_set_address": (ctypes.c_int, [_P, _P]),
+    "csa_instance_set_address_route": (ctypes.c_int, [_P, _I32]),
+    "csa_draw_household_kernel_list": (ctypes.c_int, [ctypes.c_char_p, _U64]),
     "csa_instance_draw_stats": (ctypes.c_int, [_P, _I32, _P]),
     "csa_instance_draw_stats_reset": (ctypes.c_int, [_P, _P]),
     "csa_instance_draw_stats_async": (ctypes.c_int, [_P, _P, _P]),
@@ -206,6 +210,13 @@ def draw_kernel_list():
     """Names of every draw-kernel instantiation the library can launch (csa_draw_kernel_list; no device)."""
     buf = ctypes.create_string_buffer(1 << 14)
     check(lib().csa_draw_kernel_list(buf, len(buf)))
+    return buf.value.decode().splitlines()
+
+
+def household_kernel_list():
+    """Names of the household forms of the register kernels (csa_draw_household_kernel_list; no device)."""
+    buf = ctypes.create_string_buffer(1 << 12)
+    check(lib().csa_draw_household_kernel_list(buf, len(buf)))
     return buf.value.decode().splitlines()
 
 

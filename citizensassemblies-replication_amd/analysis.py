@@ -545,6 +545,52 @@ def _with_address(enc, columns_data, check_same_address_columns):
     return _legacy.address_rings(enc.agent_ids, columns_data, check_same_address_columns)
 
 
+def _address_request(instance, columns_data, check_same_address_columns, devices=None):
+    """The household keywords of a Monte Carlo call, checked before anything touches the device: None
+    without them, else ``(columns_data, check_same_address_columns)``.  ValueError for one keyword without
+    the other, for columns that are not an (address, zip) pair, for an agent without them, and for what a
+    household-aware run is not offered with: a world of more than one rank, and ``devices=``."""
+    if columns_data is None and check_same_address_columns is None:
+        return None
+    if columns_data is None or check_same_address_columns is None:
+        raise ValueError("columns_data and check_same_address_columns go together")
+    cols = list(check_same_address_columns)
+    if len(cols) != 2:
+        raise ValueError("check_same_address_columns names two columns (address, zip), got %d" % len(cols))
+    for aid in instance.agents:
+        row = columns_data.get(aid)
+        if row is None or cols[0] not in row or cols[1] not in row:
+            raise ValueError("columns_data has no %s / %s for agent %r" % (cols[0], cols[1], aid))
+    from . import distributed as D
+    if D.world_size() > 1:
+        raise ValueError("check_same_address_columns: sharded runs (world size %d) are not offered; run on one "
+                         "process" % D.world_size())
+    if devices is not None:
+        raise ValueError("check_same_address_columns: devices= is not offered; run on one device")
+    return columns_data, cols
+
+
+class _Households:
+    """For the span of one Philox run: the instance's handle carries the address rings and draws its
+    batches on the household kernels (CSA_ADDRESS_BATCH).  Both are taken away on exit -- after the run's one
+    host wait, because csa_instance_set_address frees device memory."""
+
+    def __init__(self, enc, ring):
+        self.enc, self.ring = enc, ring
+
+    def __enter__(self):
+        L = N.lib()
+        N.check(L.csa_instance_set_address(self.enc.handle, N.ptr(self.ring)))
+        N.check(L.csa_instance_set_address_route(self.enc.handle, N.CSA_ADDRESS_BATCH))
+
+    def __exit__(self, *exc):
+        L = N.lib()
+        rc = L.csa_instance_set_address(self.enc.handle, None)
+        N.check(L.csa_instance_set_address_route(self.enc.handle, N.CSA_ADDRESS_GENERAL))
+        if exc[0] is None:
+            N.check(rc)
+
+
 def legacy_find(feature_info, agents, k, rng: str = None, *, columns_data=None,
                 check_same_address_columns=None) -> List:
     """analysis.py:141-159: one accepted panel, pick order, restarts on the device (Philox
@@ -828,7 +874,8 @@ def _multiplicity(h, d_first, d_mult, S, unique, stream):
 
 def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
                          keep_panels: bool = True, rng: str = None,
-                         devices=None) -> Tuple[ProbAllocation, PanelSet, PairHistogram]:
+                         devices=None, *, columns_data=None,
+                         check_same_address_columns=None) -> Tuple[ProbAllocation, PanelSet, PairHistogram]:
     """analysis.py:162-191 on the GPU.
 
     Returns ``({agent_id: count/S}, found_panels, pair_histogram)`` with the
@@ -847,8 +894,19 @@ def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
 
     A sharded run's found_panels hold no panels: reading them on any rank re-draws the job's panels
     on that rank's GPU (``distributed.PanelRedraw``), without a collective.
+
+    ``columns_data`` and ``check_same_address_columns`` (as ``legacy_find`` takes them) make the run
+    household-aware: every pick also removes the people still in the pool at the pick's address
+    (check_same_address, legacy.py:78-113), so no panel holds two members of a household.  In Philox mode
+    the batches run on the household forms of the register kernels where the instance fits them
+    (CSA_ADDRESS_BATCH), on draw_kernel<64, ..., true> otherwise; ``rng="mt"`` passes the rings to the host
+    draw.  One process and one device: with the keywords, a world of more than one rank and ``devices=``
+    raise ValueError before anything runs.  ``legacy_composition``, ``legacy_panel_distribution``,
+    ``legacy_panel_comparison``, ``legacy_initial_committees`` and ``legacy_maximin`` take the same
+    keywords; ``legacy_price``, ``run_legacy_or_retrieve`` and the cache do not.
     """
-    return _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, None)[:3]
+    address = _address_request(instance, columns_data, check_same_address_columns, devices)
+    return _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, None, address=address)[:3]
 
 
 # what one LEGACY run gives, the public calls take their slice: composition (a stats.CompositionHistogram) for a
@@ -856,23 +914,25 @@ def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
 LegacyRun = namedtuple("LegacyRun", "alloc panels histogram composition distribution", defaults=(None, None))
 
 
-def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, groups, multiplicity=False):
+def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, groups, multiplicity=False,
+                address=None):
     """legacy_probabilities' body, returning a LegacyRun; with ``groups`` (a stats.GroupSet) the run also
     counts the panels' composition, with ``multiplicity`` (one process, no ``devices``) how often each
-    distinct panel was drawn."""
+    distinct panel was drawn, with ``address`` (what _address_request returned) it is household-aware."""
     from . import distributed as D
     mode = rng or _legacy.RNG_MODE
     if mode not in ("philox", "mt"):
         raise ValueError("rng must be 'philox' or 'mt'")
     enc = encode_cached(instance.categories, instance.agents)
     S = int(iterations)
+    ring = _with_address(enc, *address) if address is not None else None
     if mode == "mt":
         import random
         random.seed(random_seed)
         np.random.seed(random_seed)                  # analysis.py:170 (unused by LEGACY)
         enc.check_quotas(instance.k)
         st = np.zeros(3, np.uint64)
-        picks, panels, _ = mt_draw(enc, instance.k, S, stats=st)
+        picks, panels, _ = mt_draw(enc, instance.k, S, stats=st, **({} if ring is None else {"addr_next": ring}))
         raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, host_panels=panels,
                                    host_stats=dict(zip(STAT_KEYS, (int(x) for x in st))), groups=groups,
                                    multiplicity=multiplicity)
@@ -886,6 +946,10 @@ def _legacy_run(instance, iterations, random_seed, keep_panels, rng, devices, gr
         if devices is not None:
             raw = legacy_sample_raw(enc, instance.k, S, random_seed, want_pairs=True, want_panels=keep_panels,
                                     devices=devices)
+        elif ring is not None:
+            with _Households(enc, ring):
+                raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, groups=groups,
+                                           multiplicity=multiplicity)
         else:
             raw = legacy_sample_device(enc, instance.k, S, random_seed, keep_panels=keep_panels, groups=groups,
                                        multiplicity=multiplicity)
@@ -906,7 +970,7 @@ def composition(groups, raw, S, k):
 
 
 def legacy_panel_distribution(instance: Instance, iterations: int, random_seed: int, *, rng: str = None,
-                              keep_panels: bool = True):
+                              keep_panels: bool = True, columns_data=None, check_same_address_columns=None):
     """``legacy_probabilities`` plus the run as a distribution over whole panels: returns
     ``(alloc, found_panels, pair_histogram, panel_distribution)``.
 
@@ -922,16 +986,20 @@ def legacy_panel_distribution(instance: Instance, iterations: int, random_seed: 
     ``keep_panels=False`` the spectrum and estimators work; ``top`` / ``count`` raise.  Sharded runs
     are the sibling's: with torch.distributed initialised and world size > 1 this call raises
     NotImplementedError and ``distributed.legacy_panel_distribution_distributed`` is the call to make (the
-    counts travel with the exchange's keys, 32 bytes each)."""
+    counts travel with the exchange's keys, 32 bytes each).  ``columns_data`` and
+    ``check_same_address_columns``: a household-aware run, as ``legacy_probabilities`` takes them."""
     from . import distributed as D
+    address = _address_request(instance, columns_data, check_same_address_columns)
     if D.world_size() > 1:
         raise NotImplementedError("legacy_panel_distribution: sharded runs (world size %d) are not supported here; "
                                   "call distributed.legacy_panel_distribution_distributed" % D.world_size())
-    run = _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, None, multiplicity=True)
+    run = _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, None, multiplicity=True,
+                      address=address)
     return run.alloc, run.panels, run.histogram, run.distribution
 
 
-def legacy_panel_comparison(instance: Instance, iterations: int, seed_a: int = 0, seed_b: int = 1, *, rng: str = None):
+def legacy_panel_comparison(instance: Instance, iterations: int, seed_a: int = 0, seed_b: int = 1, *, rng: str = None,
+                            columns_data=None, check_same_address_columns=None):
     """Two LEGACY runs of ``iterations`` draws each and their panel tables side by side: returns
     ``(run_a, run_b, comparison)``.
 
@@ -943,30 +1011,37 @@ def legacy_panel_comparison(instance: Instance, iterations: int, seed_a: int = 0
     csa_rows_join_async, 15 words copied): ``mass_b_on_a()`` is the held-out coverage ``run_a``'s Good-Turing
     ``coverage()`` predicts, ``cross_collision()`` the independent estimate beside ``collision_probability()``.
     With torch.distributed initialised and world size > 1 this call raises NotImplementedError, as
-    ``legacy_panel_distribution`` does."""
+    ``legacy_panel_distribution`` does.  ``columns_data`` and ``check_same_address_columns``: both runs
+    household-aware, as ``legacy_probabilities`` takes them."""
     from . import distributed as D
     from .stats import compare_panel_distributions
+    address = _address_request(instance, columns_data, check_same_address_columns)
+    hh = {} if address is None else dict(columns_data=columns_data,
+                                         check_same_address_columns=check_same_address_columns)
     if D.world_size() > 1:
         raise NotImplementedError("legacy_panel_comparison: sharded runs (world size %d) are not supported here; "
                                   "call distributed.legacy_panel_distribution_distributed" % D.world_size())
-    run_a = legacy_panel_distribution(instance, iterations, seed_a, rng=rng)
-    run_b = legacy_panel_distribution(instance, iterations, seed_b, rng=rng)
+    run_a = legacy_panel_distribution(instance, iterations, seed_a, rng=rng, **hh)
+    run_b = legacy_panel_distribution(instance, iterations, seed_b, rng=rng, **hh)
     return run_a, run_b, compare_panel_distributions(run_a[3], run_b[3])
 
 
 def legacy_initial_committees(instance: Instance, iterations: int, random_seed: int, rounds: int = None, *,
-                              rng: str = None):
+                              rng: str = None, columns_data=None, check_same_address_columns=None):
     """The reference's _generate_initial_committees (xmin.py:229-290) over a LEGACY run's distinct panels instead
     of an ILP: ``legacy_panel_distribution(instance, iterations, random_seed, rng=rng)`` followed by its
     ``initial_committees(rounds)`` (``rounds`` defaults to 3 n, leximin.py:373; csa_rows_mw_cover_async and
     csa_rows_first_holder_async over the run's sorted table on the device).  Returns ``(committees,
     covered_agents, output_lines)``, what _expand_distribution_leximin takes as ``initial_committees`` /
-    ``initial_covered_agents``.  World size > 1 raises NotImplementedError, as ``legacy_panel_distribution``."""
-    return legacy_panel_distribution(instance, iterations, random_seed, rng=rng)[3].initial_committees(rounds)
+    ``initial_covered_agents``.  World size > 1 raises NotImplementedError, as ``legacy_panel_distribution``;
+    ``columns_data`` and ``check_same_address_columns`` are passed on to it."""
+    run = legacy_panel_distribution(instance, iterations, random_seed, rng=rng, columns_data=columns_data,
+                                    check_same_address_columns=check_same_address_columns)
+    return run[3].initial_committees(rounds)
 
 
 def legacy_maximin(instance: Instance, iterations: int, random_seed: int, rounds: int = None, *, shrink: float = 0.8,
-                   resync: int = 16, rng: str = None):
+                   resync: int = 16, rng: str = None, columns_data=None, check_same_address_columns=None):
     """How fair could a lottery over exactly the panels a LEGACY run drew be made: ``legacy_panel_distribution(
     instance, iterations, random_seed, rng=rng)`` followed by its ``maximin(rounds, shrink, resync)`` (``rounds``
     defaults to 3 n; csa_rows_maximin_async over the run's sorted table on the device).  Returns a
@@ -974,8 +1049,11 @@ def legacy_maximin(instance: Instance, iterations: int, random_seed: int, rounds
     ``legacy_portfolio_overlap`` take, and ``lower <= z* <= upper`` for the optimum z* of the reference's first
     leximin stage over the drawn panels (xmin.py:293-321) -- ``lower`` also bounds LEXIMIN's minimum selection
     probability from below, and the portfolio is a warm start for a caller who has the solvers.  World size > 1
-    raises NotImplementedError, as ``legacy_panel_distribution``."""
-    return legacy_panel_distribution(instance, iterations, random_seed, rng=rng)[3].maximin(rounds, shrink, resync)
+    raises NotImplementedError, as ``legacy_panel_distribution``; ``columns_data`` and
+    ``check_same_address_columns`` are passed on to it."""
+    run = legacy_panel_distribution(instance, iterations, random_seed, rng=rng, columns_data=columns_data,
+                                    check_same_address_columns=check_same_address_columns)
+    return run[3].maximin(rounds, shrink, resync)
 
 
 def legacy_price(instance: Instance, weights, iterations: int, random_seed: int, chunk: int = 1 << 20):
@@ -1041,7 +1119,7 @@ def legacy_portfolio_overlap(instance: Instance, distribution, portfolio, probab
 
 
 def legacy_composition(instance: Instance, iterations: int, random_seed: int, groups, *, rng: str = None,
-                       keep_panels: bool = True):
+                       keep_panels: bool = True, columns_data=None, check_same_address_columns=None):
     """``legacy_probabilities`` plus what its panels look like as a whole: returns
     ``(alloc, found_panels, pair_histogram, composition)``.
 
@@ -1053,9 +1131,12 @@ def legacy_composition(instance: Instance, iterations: int, random_seed: int, gr
     the drawn panels while they are in device memory, its table returned in the call's one host copy.
     ``rng="mt"`` runs the same pass over the host-drawn panels.  With torch.distributed initialised
     and world size > 1 the call is sharded like ``legacy_probabilities`` and every rank returns the
-    whole job's table (summed over the ranks)."""
+    whole job's table (summed over the ranks).  ``columns_data`` and ``check_same_address_columns``: a
+    household-aware run, as ``legacy_probabilities`` takes them (one rank only); over
+    ``stats.household_groups`` its table then holds nothing at two members or more."""
+    address = _address_request(instance, columns_data, check_same_address_columns)
     _check_groups(instance, groups)
-    return _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, groups)[:4]
+    return _legacy_run(instance, iterations, random_seed, keep_panels, rng, None, groups, address=address)[:4]
 
 
 def finish(instance, enc, raw, S):

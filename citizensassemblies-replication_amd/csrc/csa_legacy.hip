@@ -1801,6 +1801,7 @@ struct csa_instance {
     // start state; null when neither register kernel fits the instance)
     uint64_t *d_image = nullptr;
     int32_t *d_addr_next = nullptr;  // same-address rings (csa_instance_set_address) or null
+    int32_t address_route = CSA_ADDRESS_GENERAL;  // csa_instance_set_address_route
     int32_t max_abs = 0;  // max |fmin| / |sel0| bound for the cross-multiplication range check
     bool zero_max_min = false;  // some feature has max 0 and min > 0 (draw_batch_kernel excludes it)
     // some feature starts with selected >= max > 0: the lane / wide kernels test "selected == max" as
@@ -2409,6 +2410,17 @@ int csa_instance_set_address(csa_instance *I, const int32_t *addr_next) {
     return CSA_OK;
 }
 
+int csa_instance_set_address_route(csa_instance *I, int32_t route) {
+    if (route != CSA_ADDRESS_GENERAL && route != CSA_ADDRESS_BATCH)
+        return fail(CSA_E_INVALID, "unknown address route %d", route);
+    if (!I) return fail(CSA_E_INVALID, "null instance");
+    if (I->address_route != route) {
+        I->address_route = route;
+        ++I->gen;  // the replicas of csa_legacy_sample_devices take it over
+    }
+    return CSA_OK;
+}
+
 int csa_pair_histogram_async(const int64_t *d_pairs, int32_t n, uint64_t *d_hist, uint64_t n_bins,
                              uint64_t *d_overflow, void *stream) {
     if (n < 0 || !d_pairs || !d_hist || !d_overflow || n_bins == 0) return fail(CSA_E_INVALID, "pair histogram: bad arguments");
@@ -2758,6 +2770,21 @@ int csa_draw_kernel_list(char *buf, uint64_t len) {
     }
     if (!buf || len < all.size() + 1)
         return fail(CSA_E_INVALID, "draw kernel list: the buffer needs %zu bytes", all.size() + 1);
+    memcpy(buf, all.c_str(), all.size() + 1);
+    return CSA_OK;
+}
+
+// The rows of kHouseholdKernels (draw_dispatch.inc), under csa_draw_kernel_list's contract.
+int csa_draw_household_kernel_list(char *buf, uint64_t len) {
+    std::string all;
+    char name[128];
+    for (const DrawConfig &c : kHouseholdKernels) {
+        draw_config_name(c, name, sizeof name);
+        all += name;
+        all += '\n';
+    }
+    if (!buf || len < all.size() + 1)
+        return fail(CSA_E_INVALID, "household kernel list: the buffer needs %zu bytes", all.size() + 1);
     memcpy(buf, all.c_str(), all.size() + 1);
     return CSA_OK;
 }
@@ -3359,7 +3386,8 @@ static int shard_instance(csa_instance *I, int s, int dev, csa_instance **out) {
     if (I->replica_gen[s] != I->gen) {
         if ((rc = csa_instance_set_state(R, I->sel0.data(), I->rem0h.empty() ? nullptr : I->rem0h.data(),
                                          I->present0h.empty() ? nullptr : I->present0h.data())) ||
-            (rc = csa_instance_set_address(R, I->addr_h.empty() ? nullptr : I->addr_h.data())))
+            (rc = csa_instance_set_address(R, I->addr_h.empty() ? nullptr : I->addr_h.data())) ||
+            (rc = csa_instance_set_address_route(R, I->address_route)))
             return rc;
         I->replica_gen[s] = I->gen;
     }

@@ -13,6 +13,7 @@ struct DrawConfig {
     int np = 8;              // solo (FN >= 16) / lane: slack bit planes, csa_instance::max_slack < 2^np
     bool k8 = false;         // solo / lane: the 8-bit need keys carrying their index (csa_instance::need8)
     const void *fn = nullptr;
+    bool hh = false;         // solo / lane: the household form (kHouseholdKernels), np = 8
     // lanes that draw one panel together (draw_kernel's and draw_wide_kernel's G)
     int lanes() const {
         switch (family) {
@@ -69,8 +70,29 @@ const DrawConfig kDrawKernels[] = {
 };
 static_assert(sizeof kDrawKernels / sizeof kDrawKernels[0] == 115, "the set of built draw kernels is fixed");
 
+// The household forms of the register kernels (CSA_ADDRESS_BATCH), a table of their own: every built
+// FN / WN / K8 at 8 slack planes, which hold every instance the register kernels take.
+#define CSA_SOLO_HH_ROW(FN, WN, K8) \
+    {DrawFamily::solo, FN, WN, 8, K8, CSA_KERNEL(draw_solo_hh_kernel<FN, WN, K8>), true},
+#define CSA_SOLO_HH8(WN) CSA_BOTH_K8(CSA_SOLO_HH_ROW, 8, WN)
+#define CSA_SOLO_HH16(WN) CSA_BOTH_K8(CSA_SOLO_HH_ROW, 16, WN)
+#define CSA_LANE_HH_ROW(FN, WN, K8) \
+    {DrawFamily::lane, FN, WN, 8, K8, CSA_KERNEL(draw_lane_hh_kernel<FN, WN, lane_sk(WN), K8>), true},
+#define CSA_LANE_HH32(WN) CSA_BOTH_K8(CSA_LANE_HH_ROW, 32, WN)
+
+const DrawConfig kHouseholdKernels[] = {CSA_REG_WN(CSA_SOLO_HH8) CSA_REG_WN(CSA_SOLO_HH16) CSA_REG_WN(CSA_LANE_HH32)};
+static_assert(sizeof kHouseholdKernels / sizeof kHouseholdKernels[0] == 30, "the set of household kernels is fixed");
+
 // the row with c's family and parameters, into c; false when none is built
 bool find_draw_kernel(DrawConfig &c) {
+    if (c.hh) {
+        for (const DrawConfig &r : kHouseholdKernels)
+            if (r.family == c.family && r.fdim == c.fdim && r.wdim == c.wdim && r.k8 == c.k8) {
+                c.fn = r.fn;
+                return true;
+            }
+        return false;
+    }
     for (const DrawConfig &r : kDrawKernels)
         if (r.family == c.family && r.fdim == c.fdim && r.wdim == c.wdim && r.np == c.np && r.k8 == c.k8) {
             c.fn = r.fn;
@@ -89,9 +111,10 @@ int slack_planes(int max_slack) { return max_slack < 32 ? 5 : max_slack < 128 ? 
 // (F <= 64, W <= 256) or 64.  Pick-order / single-attempt draws (general mode) use
 // draw_kernel<64, ..., true>.  CSA_DRAW_KERNEL=solo|lane|wide|16|64 forces a batch kernel the instance
 // fits (parity tests of every layout).  The family and its bucketed parameters then name one row of
-// kDrawKernels (find_draw_kernel).
+// kDrawKernels (find_draw_kernel).  An instance with address rings draws on draw_kernel<64, ..., true>,
+// except a batch draw under CSA_ADDRESS_BATCH of an instance a register kernel takes: that one runs
+// the kernel's household form (kHouseholdKernels; CSA_DRAW_KERNEL does not apply).
 int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
-    general = general || I->d_addr_next;  // same-address deletions: draw_kernel<64, ..., true> only
     const bool reg_ok = I->F <= 32 && I->d_pmask && !I->zero_max_min && I->W <= 32 && I->max_abs < 32768 &&
                         !I->sel_over_max && I->max_slack <= 255;
     const bool lane_ok = reg_ok && I->F > 16;  // built for FN = 32 only
@@ -101,11 +124,13 @@ int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
     // example_large_200 281 vs 252 M panels/s, example_small_20 2950 vs 2490); at F = 32 the state needs
     // 165 VGPRs and the two-lane kernel's 4 waves/SIMD win (sf_e 262 vs 247)
     const bool solo_ok = reg_ok && I->F <= 16;
+    const bool hh = !general && I->d_addr_next && I->address_route == CSA_ADDRESS_BATCH && (solo_ok || lane_ok);
+    general = general || (I->d_addr_next && !hh);  // same-address deletions otherwise: draw_kernel<64, ..., true> only
     using DF = DrawFamily;
     c = DrawConfig();
     c.family = general ? DF::g64_general : solo_ok ? DF::solo : lane_ok ? DF::lane : wide_ok ? DF::wide
                : g16_ok ? DF::g16 : DF::g64;
-    const char *e = general ? nullptr : getenv("CSA_DRAW_KERNEL");
+    const char *e = general || hh ? nullptr : getenv("CSA_DRAW_KERNEL");
     if (e) {
         // the register kernels are built for the shapes they win on only (solo F <= 16, lane F > 16)
         if (!strcmp(e, "solo") && solo_ok) c.family = DF::solo;
@@ -117,7 +142,8 @@ int pick_draw_config(const csa_instance *I, bool general, DrawConfig &c) {
     if (c.reg()) {
         reg_kernel_shape(I, c.fdim, c.wdim);
         c.k8 = I->need8;
-        c.np = c.fdim >= 16 ? slack_planes(I->max_slack) : 8;
+        c.np = c.fdim >= 16 && !hh ? slack_planes(I->max_slack) : 8;
+        c.hh = hh;
     } else if (c.family == DF::wide) {
         const int fpl = (I->F + 7) / 8;
         c.fdim = fpl <= 2 ? 2 : fpl <= 4 ? 4 : fpl <= 5 ? 5 : 8;
@@ -140,10 +166,12 @@ void draw_config_name(const DrawConfig &c, char *buf, size_t len) {
     const char *k8 = c.k8 ? "true" : "false";
     switch (c.family) {
         case DrawFamily::solo:
-            snprintf(buf, len, "draw_solo_kernel<%d, %d, %d, %s>", c.fdim, c.wdim, c.np, k8);
+            if (c.hh) snprintf(buf, len, "draw_solo_hh_kernel<%d, %d, %s>", c.fdim, c.wdim, k8);
+            else snprintf(buf, len, "draw_solo_kernel<%d, %d, %d, %s>", c.fdim, c.wdim, c.np, k8);
             break;
         case DrawFamily::lane:
-            snprintf(buf, len, "draw_lane_kernel<%d, %d, %d, %d, %s>", c.fdim, c.wdim, lane_sk(c.wdim), c.np, k8);
+            if (c.hh) snprintf(buf, len, "draw_lane_hh_kernel<%d, %d, %d, %s>", c.fdim, c.wdim, lane_sk(c.wdim), k8);
+            else snprintf(buf, len, "draw_lane_kernel<%d, %d, %d, %d, %s>", c.fdim, c.wdim, lane_sk(c.wdim), c.np, k8);
             break;
         case DrawFamily::wide:
             snprintf(buf, len, "draw_wide_kernel<%d, %d, %d>", c.lanes(), c.fdim, c.wdim);
@@ -168,8 +196,8 @@ DrawGeometry draw_geometry(const DrawConfig &c, const csa_instance *I, int32_t k
                 : c.family == DrawFamily::wide ? kWideThreads
                                                : draw_threads(c.fdim, c.wdim);
     g.panels_wg = g.threads / c.lanes();
-    g.lds = c.family == DrawFamily::lane   ? lane_lds_bytes(c.fdim, c.wdim, I->n)
-            : c.family == DrawFamily::solo ? solo_lds_bytes(c.fdim, c.wdim, I->n)
+    g.lds = c.family == DrawFamily::lane   ? lane_lds_bytes(c.fdim, c.wdim, I->n, c.hh)
+            : c.family == DrawFamily::solo ? solo_lds_bytes(c.fdim, c.wdim, I->n, c.hh)
             : c.family == DrawFamily::wide ? wide_lds_bytes(c.lanes(), c.fdim, c.wdim)
                                            : draw_lds_bytes(c.lanes(), c.fdim, c.wdim, I->W, k, g.panels_wg);
     return g;

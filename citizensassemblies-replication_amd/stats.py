@@ -245,6 +245,24 @@ def agent_groups(instance, groups):
     return GroupSet(labels, _pack_members(member, enc.W), member.sum(axis=1))
 
 
+def household_groups(agent_ids, columns_data, check_same_address_columns):
+    """One group per household of at least two agents: the rings of ``legacy.address_rings`` over
+    ``agent_ids`` (an encoding's ``agent_ids``), labelled by their (address, zip) values, in order of each
+    household's first agent.  A household-aware run's ``legacy_composition`` over it shows no panel that
+    holds two members of a household: every count at 2 or above is zero."""
+    c0, c1 = check_same_address_columns[0], check_same_address_columns[1]
+    homes = {}
+    for p, aid in enumerate(agent_ids):
+        row = columns_data[aid]
+        homes.setdefault((row[c0], row[c1]), []).append(p)
+    labels = [key for key, members in homes.items() if len(members) >= 2]
+    n = len(agent_ids)
+    member = np.zeros((len(labels), n), np.bool_)
+    for g, key in enumerate(labels):
+        member[g, homes[key]] = True
+    return GroupSet(labels, _pack_members(member, (n + 63) // 64), member.sum(axis=1))
+
+
 def group_hist_host(masks, panels, bins):
     """csa_group_hist_async's contract in numpy: int64[G, bins], hist[g][c] = number of panels with
     popcount(panel & mask_g) == c.  A count >= bins raises CsaError(CSA_E_INVALID), as the device's

@@ -103,9 +103,24 @@ int csa_instance_draw_stats_async(csa_instance *inst, uint64_t *d_out, void *str
  * an address (the check_same_address_columns values) into rings, agent order: addr_next[p] = the
  * next agent at p's address, p itself when p lives alone.  With a ring set, every pick deletes
  * the remaining agents at its address (really_delete_person(selected=False)) before the
- * full-category cascades; all draws of the instance then run draw_kernel<64, ..., true>.
+ * full-category cascades; all draws of the instance then run draw_kernel<64, ..., true>, unless
+ * csa_instance_set_address_route says otherwise.
  * NULL removes the rings (the default: the reference harness passes False, analysis.py:150). */
 int csa_instance_set_address(csa_instance *inst, const int32_t *addr_next);
+
+/* Where the draws of an instance with address rings run.  CSA_ADDRESS_GENERAL (the default): all of
+ * them on draw_kernel<64, ..., true>, one panel per wavefront; csa_draw_xt_async then reports
+ * written == 0.  CSA_ADDRESS_BATCH: a batch draw -- no pick order (csa_legacy_find's picks), no single
+ * attempt, no state export, no index list -- of an instance that the register kernels take (F <= 32,
+ * n <= 2048 and their other conditions, csrc/draw_dispatch.inc) runs the household form of its
+ * register kernel, draw_solo_hh_kernel<FN, WN, K8> or draw_lane_hh_kernel<FN, WN, SK, K8>: same
+ * panels, attempts and statistics, csa_draw_xt_async reports written == 1, csa_draw_picks_async is
+ * offered.  Every other request and every other shape runs as under CSA_ADDRESS_GENERAL.  Without
+ * rings the route changes nothing.  An unknown route is CSA_E_INVALID.  csa_legacy_sample_devices
+ * copies the route to its replicas. */
+#define CSA_ADDRESS_GENERAL 0
+#define CSA_ADDRESS_BATCH 1
+int csa_instance_set_address_route(csa_instance *inst, int32_t route);
 
 /* ---- host-buffer API (blocking) ------------------------------------------ */
 
@@ -258,7 +273,9 @@ int csa_panel_hash_async(const uint64_t *d_panels, uint64_t n_panels, int32_t W,
                          void *stream);
 
 /* Name of the draw kernel csa_draw_async launches for this instance and k
- * (e.g. "draw_lane_kernel<32, 28, 14, 7, true>"), for matching profiler output. */
+ * (e.g. "draw_lane_kernel<32, 28, 14, 7, true>"), for matching profiler output; for an instance
+ * with address rings the household form where CSA_ADDRESS_BATCH runs it (e.g.
+ * "draw_lane_hh_kernel<32, 28, 14, true>"), else the batch kernel's name (never a GENERAL one). */
 int csa_draw_kernel_name(const csa_instance *inst, int32_t k, char *buf, uint64_t len);
 
 /* Names of every draw-kernel instantiation the dispatcher can resolve (batch draws and the GENERAL
@@ -267,6 +284,9 @@ int csa_draw_kernel_name(const csa_instance *inst, int32_t k, char *buf, uint64_
  * looks its kernel up in (kDrawKernels, csrc/draw_dispatch.inc), in no particular order.  Needs no device.
  * CSA_E_INVALID when buf is NULL or len is too small; csa_last_error then names the size needed. */
 int csa_draw_kernel_list(char *buf, uint64_t len);
+/* The same for the household forms of the register kernels (CSA_ADDRESS_BATCH), which
+ * csa_draw_kernel_list does not name: 30 lines, under the same contract. */
+int csa_draw_household_kernel_list(char *buf, uint64_t len);
 
 /* Bit-transpose + per-person count.  Panels (n_panels*W) -> d_xt, the
  * panel-indicator matrix transposed and packed in two 32-bit planes per
