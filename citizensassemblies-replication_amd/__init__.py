@@ -48,6 +48,12 @@ legacy_maximin -- how fair a lottery over exactly the drawn panels can be made, 
 stage over them solved by multiplicative weights with a lower and an upper bound (PanelMaximin), no LP
 solver; rows_maximin_host is the numpy contract
 
+plus the Nash-welfare lottery over such a table (csa_rows_nash_async, csa_rows_marginals_async):
+PanelDistribution.nash(rounds) / legacy_nash -- the lottery over exactly the drawn panels with the greatest
+geometric mean of selection probabilities, by Cover's multiplicative iteration with a certificate
+geometric_mean <= optimum <= upper (PanelNash, NashState), no solver; rows_nash_host and rows_marginals_host
+are the numpy contracts
+
 plus xmin._get_panel_not_in_portfolio_if_possible (XMIN's LEGACY caller,
 xmin.py:464-474) on the device.
 """
@@ -70,6 +76,8 @@ from .stats import (PanelPrice, rows_first_holder_host, rows_mw_cover_host, rows
                     rows_score_host)
 from .analysis import legacy_maximin  # noqa: F401
 from .stats import MaximinState, PanelMaximin, rows_maximin_host  # noqa: F401
+from .analysis import legacy_nash  # noqa: F401
+from .stats import NashState, PanelNash, rows_marginals_host, rows_nash_host  # noqa: F401
 from .stats import household_groups  # noqa: F401
 from . import _native, xmin  # noqa: F401
 
@@ -85,4 +93,5 @@ __all__ = ["Instance", "read_instance", "encode", "SelectionError", "check_min_c
            "compare_panel_distributions", "portfolio_overlap", "rows_join_host", "rows_find_host",
            "legacy_initial_committees", "legacy_price", "PanelPrice", "rows_score_host", "rows_price_host",
            "rows_mw_cover_host", "rows_first_holder_host", "legacy_maximin", "PanelMaximin", "MaximinState",
-           "rows_maximin_host", "household_groups"]
+           "rows_maximin_host", "household_groups", "legacy_nash", "PanelNash", "NashState", "rows_nash_host",
+           "rows_marginals_host"]

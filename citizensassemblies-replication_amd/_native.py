@@ -43,6 +43,7 @@ CSA_PRICE_NONE = 0xFFFFFFFFFFFFFFFF  # d_best[0] of an empty table
 CSA_ADDRESS_GENERAL = 0  # csa_instance_set_address_route: every ring draw on draw_kernel<64, ..., true>
 CSA_ADDRESS_BATCH = 1    # batch draws of a register-kernel instance on the kernel's household form
 CSA_MAXIMIN_START = 0x1  # csa_rows_maximin_async: initialise the state before the rounds
+CSA_NASH_START = 0x1     # csa_rows_nash_async: start from the multiplicities (or uniform) before the rounds
 
 # every symbol include/csa_legacy.h declares, with its ctypes signature
 _P = ctypes.c_void_p
@@ -131,6 +132,12 @@ SIGNATURES = {
     "csa_rows_maximin_scratch_bytes": (_U64, [_U64, _I32]),
     "csa_rows_maximin_async": (ctypes.c_int, [_P, _P, _U64, _I32, _I32, _U32, ctypes.c_double, _U32, _U32, _P, _P, _P,
                                               _P, _P, _P, _P, _U64, _P]),
+    "csa_rows_nash_tile": (_U32, []),
+    "csa_rows_marginals_scratch_bytes": (_U64, [_U64, _I32]),
+    "csa_rows_marginals_async": (ctypes.c_int, [_P, _P, _U64, _I32, _I32, _P, _P, _P, _P, _U64, _P]),
+    "csa_rows_nash_scratch_bytes": (_U64, [_U64, _I32]),
+    "csa_rows_nash_async": (ctypes.c_int, [_P, _P, _U64, _I32, _I32, _U32, _U32, _P, _U64, _P, _P, _P, _P, _P, _U64,
+                                           _P]),
 }
 
 _lib = None

@@ -902,7 +902,7 @@ def legacy_probabilities(instance: Instance, iterations: int, random_seed: int,
     (CSA_ADDRESS_BATCH), on draw_kernel<64, ..., true> otherwise; ``rng="mt"`` passes the rings to the host
     draw.  One process and one device: with the keywords, a world of more than one rank and ``devices=``
     raise ValueError before anything runs.  ``legacy_composition``, ``legacy_panel_distribution``,
-    ``legacy_panel_comparison``, ``legacy_initial_committees`` and ``legacy_maximin`` take the same
+    ``legacy_panel_comparison``, ``legacy_initial_committees``, ``legacy_maximin`` and ``legacy_nash`` take the same
     keywords; ``legacy_price``, ``run_legacy_or_retrieve`` and the cache do not.
     """
     address = _address_request(instance, columns_data, check_same_address_columns, devices)
@@ -1054,6 +1054,23 @@ def legacy_maximin(instance: Instance, iterations: int, random_seed: int, rounds
     run = legacy_panel_distribution(instance, iterations, random_seed, rng=rng, columns_data=columns_data,
                                     check_same_address_columns=check_same_address_columns)
     return run[3].maximin(rounds, shrink, resync)
+
+
+def legacy_nash(instance: Instance, iterations: int, random_seed: int, rounds: int = 200, *, start: str = "legacy",
+                rng: str = None, columns_data=None, check_same_address_columns=None):
+    """Which lottery over exactly the panels a LEGACY run drew has the greatest geometric mean of selection
+    probabilities, and how much of it does LEGACY leave on the table: ``legacy_panel_distribution(instance,
+    iterations, random_seed, rng=rng)`` followed by its ``nash(rounds, start)`` (csa_rows_nash_async over the
+    run's sorted table on the device).  Returns a ``stats.PanelNash``: a ``portfolio()`` that
+    ``portfolio_probabilities``, ``portfolio_composition`` and ``legacy_portfolio_overlap`` take, and
+    ``start_geometric_mean <= geometric_mean <= optimum <= upper`` for the Nash-welfare optimum over the drawn
+    panels -- the geometric mean of ``compute_prob_allocation_stats`` (analysis.py:231-255) as an objective.
+    ``start="legacy"`` starts from the run's own multiplicities, ``"uniform"`` from equal probabilities.  World
+    size > 1 raises NotImplementedError, as ``legacy_panel_distribution``; ``columns_data`` and
+    ``check_same_address_columns`` are passed on to it."""
+    run = legacy_panel_distribution(instance, iterations, random_seed, rng=rng, columns_data=columns_data,
+                                    check_same_address_columns=check_same_address_columns)
+    return run[3].nash(rounds, start)
 
 
 def legacy_price(instance: Instance, weights, iterations: int, random_seed: int, chunk: int = 1 << 20):

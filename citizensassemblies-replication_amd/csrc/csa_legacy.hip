@@ -4143,3 +4143,115 @@ int csa_rows_maximin_async(const uint64_t *d_rows, const uint64_t *d_len, uint64
 }
 
 }  // extern "C"
+
+// The Nash-welfare lottery over such a table (rows_nash.inc) stands last, for the same reason.
+namespace {
+#include "rows_nash.inc"
+
+// the marginal pass and its finish over p: part | psum_part at `part`; with first holders also inv and m
+void rn_marginals(hipStream_t st, const uint64_t *d_rows, const unsigned long long *len, uint64_t cap, int W, int n,
+                  int empty_too, const double *prob, double *part, const uint32_t *first, double *marginals,
+                  double *inv, double *psum) {
+    const uint64_t tiles = rn_tiles(cap);
+    double *psum_part = part + tiles * (uint64_t)64 * W;
+    if (tiles)
+        hipLaunchKernelGGL(rn_marginal_kernel<>, dim3((unsigned)tiles, (unsigned)((W + kRnWaves * kRnWords - 1) / (kRnWaves * kRnWords))),
+                           dim3(kRnThreads), 0, st, d_rows, len, cap, W, prob, part, psum_part);
+    const unsigned blocks = (unsigned)(((size_t)64 * W + kRpThreads - 1) / kRpThreads) + 1;
+    hipLaunchKernelGGL(rn_finish_kernel<>, dim3(blocks), dim3(kRpThreads), 0, st, len, cap, W, n, empty_too,
+                       (const double *)part, (const double *)psum_part, first, marginals, inv, psum);
+}
+}  // namespace
+
+extern "C" {
+
+uint32_t csa_rows_nash_tile(void) { return kRnTile; }
+
+uint64_t csa_rows_nash_scratch_bytes(uint64_t cap, int32_t W) { return W < 1 ? 0 : rn_scratch_bytes(cap, W); }
+
+uint64_t csa_rows_marginals_scratch_bytes(uint64_t cap, int32_t W) { return W < 1 ? 0 : rn_part_bytes(cap, W); }
+
+int csa_rows_marginals_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                             const double *d_prob, double *d_marginals, double *d_psum, void *d_scratch,
+                             uint64_t scratch_bytes, void *stream) {
+    if (int rc = rp_check("rows marginals", d_rows, d_len, cap, W, n)) return rc;
+    if (!d_marginals || !d_psum || (cap && !d_prob)) return fail(CSA_E_INVALID, "rows marginals: NULL prob, marginals or psum");
+    const uint64_t need = rn_part_bytes(cap, W);
+    if (need && (!d_scratch || scratch_bytes < need || ((uintptr_t)d_scratch & 7)))
+        return fail(CSA_E_INVALID, "rows marginals: scratch_bytes < csa_rows_marginals_scratch_bytes, or scratch NULL "
+                                   "or not 8-byte aligned");
+    {
+        const void *buf[] = {d_marginals, d_psum, d_scratch, d_prob, d_rows, d_len};
+        const uint64_t bytes[] = {(uint64_t)n * 8, 8, need, cap * 8, cap * (uint64_t)W * 8, 8};
+        for (int a = 0; a < 3; ++a)   // what is written, against everything after it
+            for (int b = a + 1; b < 6; ++b)
+                if (rs_overlap(buf[a], bytes[a], buf[b], bytes[b]))
+                    return fail(CSA_E_INVALID, "rows marginals: buffers %d and %d overlap", a, b);
+    }
+    rn_marginals((hipStream_t)stream, d_rows, reinterpret_cast<const unsigned long long *>(d_len), cap, (int)W, (int)n,
+                 1, d_prob, static_cast<double *>(d_scratch), nullptr, d_marginals, nullptr, d_psum);
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+int csa_rows_nash_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                        uint32_t rounds, uint32_t flags, const uint32_t *d_mult, uint64_t total, double *d_prob,
+                        double *d_scores, double *d_marginals, uint64_t *d_state, void *d_scratch,
+                        uint64_t scratch_bytes, void *stream) {
+    if (int rc = rp_check("rows nash", d_rows, d_len, cap, W, n)) return rc;
+    if (flags & ~CSA_NASH_START) return fail(CSA_E_INVALID, "rows nash: unknown flags 0x%x", flags);
+    const bool start = flags & CSA_NASH_START;
+    if (!d_marginals || !d_state || (cap && (!d_prob || !d_scores)))
+        return fail(CSA_E_INVALID, "rows nash: NULL prob, scores, marginals or state");
+    if (start && d_mult && total == 0) return fail(CSA_E_INVALID, "rows nash: multiplicities with a total of 0");
+    const uint64_t need = rn_scratch_bytes(cap, W);
+    if (!d_scratch || scratch_bytes < need || ((uintptr_t)d_scratch & 7))
+        return fail(CSA_E_INVALID, "rows nash: scratch_bytes < csa_rows_nash_scratch_bytes, or scratch NULL or not "
+                                   "8-byte aligned");
+    {
+        const void *buf[] = {d_prob, d_scores, d_marginals, d_state, d_scratch, d_mult, d_rows, d_len};
+        const uint64_t bytes[] = {cap * 8, cap * 8, (uint64_t)n * 8, 32, need, d_mult ? cap * 4 : 0,
+                                  cap * (uint64_t)W * 8, 8};
+        for (int a = 0; a < 5; ++a)   // what is written, against everything after it
+            for (int b = a + 1; b < 8; ++b)
+                if (rs_overlap(buf[a], bytes[a], buf[b], bytes[b]))
+                    return fail(CSA_E_INVALID, "rows nash: buffers %d and %d overlap", a, b);
+    }
+    if (!start && rounds == 0) return CSA_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned long long *len = reinterpret_cast<const unsigned long long *>(d_len);
+    const uint64_t nb = rp_blocks(cap);
+    unsigned char *base = static_cast<unsigned char *>(d_scratch);
+    uint64_t *slab = reinterpret_cast<uint64_t *>(base);
+    double *part = reinterpret_cast<double *>(base + 16 * nb);
+    double *inv = reinterpret_cast<double *>(base + 16 * nb + rn_part_bytes(cap, W));
+    uint32_t *first = reinterpret_cast<uint32_t *>(inv + (size_t)64 * W);
+    double *psum = reinterpret_cast<double *>(first + (size_t)64 * W);
+    uint64_t *m_word = reinterpret_cast<uint64_t *>(psum + 1);
+    if (start && nb)
+        hipLaunchKernelGGL(rn_start_kernel<>, dim3((unsigned)nb), dim3(kRpThreads), 0, st, len, cap, d_mult, total, d_prob);
+    HIPCHK(hipMemsetAsync(first, 0xFF, (size_t)64 * W * 4, st));
+    if (cap) {
+        const uint64_t words = cap * (uint64_t)W;
+        const unsigned grid =
+            (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((words + 8 * kRpThreads - 1) / (8 * kRpThreads), 2048));
+        hipLaunchKernelGGL(rp_first_holder_kernel<>, dim3(grid), dim3(kRpThreads), (size_t)64 * W * 4, st, d_rows, len,
+                           cap, (int)W, (int)n, first);
+    }
+    hipLaunchKernelGGL(rn_held_kernel<>, dim3(1), dim3(kRpThreads), 0, st, (const uint32_t *)first, (int)n, m_word);
+    for (uint32_t r = start ? 0 : 1; r <= rounds; ++r) {   // pass 0 is the start's
+        if (r && nb)
+            hipLaunchKernelGGL(rn_step_kernel<>, dim3((unsigned)nb), dim3(kRpThreads), 0, st, len, cap,
+                               (const double *)d_scores, (const uint64_t *)m_word, d_prob);
+        rn_marginals(st, d_rows, len, cap, (int)W, (int)n, r == 0, d_prob, part, first, d_marginals, inv, psum);
+        if (nb)
+            hipLaunchKernelGGL(rp_score_kernel<>, dim3((unsigned)nb), dim3(kRpThreads), rp_score_lds(W), st, d_rows, len,
+                               cap, (int)W, (int)n, (const double *)inv, d_scores, slab);
+        hipLaunchKernelGGL(rn_bound_kernel<>, dim3(1), dim3(kRpThreads), kRpBestLds, st, (const uint64_t *)slab, nb,
+                           (const double *)psum, (const uint64_t *)m_word, r == 0 ? 1 : 0, d_state);
+    }
+    HIPCHK(hipGetLastError());
+    return CSA_OK;
+}
+
+}  // extern "C"

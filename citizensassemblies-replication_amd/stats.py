@@ -860,6 +860,47 @@ class PanelDistribution:
             picked = _rows_at(t, picks, False)
         return PanelMaximin(picks, picked, cover, covered, upper, n, ids)
 
+    def nash(self, rounds=200, start="legacy"):
+        """Which lottery over exactly the panels this run drew has the greatest geometric mean of selection
+        probabilities (the third headline statistic of ``compute_prob_allocation_stats``), and how much of it
+        does LEGACY leave on the table?  The Nash-welfare lottery -- the maximum product of the probabilities of
+        the agents some drawn panel holds -- by ``rounds`` rounds of Cover's multiplicative iteration over the
+        sorted table: on its device csa_rows_nash_async (plain launches; a START-only call, a clone of its
+        marginals, the rounds, then one concatenated copy and one host wait), on the host ``rows_nash_host``.
+        ``start="legacy"`` starts from the run's multiplicities / S, so round 0 is LEGACY's own lottery over these
+        panels; ``start="uniform"`` from equal probabilities.  Returns a ``PanelNash``: the lottery, each agent's
+        selection probability under it, and ``geometric_mean <= optimum <= upper``.  No LP solver is involved.
+        An empty run gives an empty result without a call; ValueError for rounds < 0 or another ``start``."""
+        n, rounds = self._n, int(rounds)
+        if rounds < 0:
+            raise ValueError("rounds must not be negative")
+        if start not in ("legacy", "uniform"):
+            raise ValueError("start must be 'legacy' or 'uniform', not %r" % (start,))
+        ids = list(self._ids)
+        if not self.distinct:
+            return PanelNash(None, np.zeros(0), np.zeros(n), 0.0, np.zeros(n), 0.0, np.inf, 0, PRICE_NONE, n, ids)
+        t = self.table()
+        ops, device = _table_ops(t)
+        mult = t.mult if start == "legacy" else None
+        if device:
+            import torch
+            D = self.distinct
+            with torch.cuda.stream(ops.stream):
+                b = ops.nash(t, n, 0, mult, self.S)
+                pi0, block0 = b.marginals.clone(), b.block.clone()
+                b = ops.nash(t, n, rounds, state=b)
+                h = torch.cat([b.block, block0[3:4], b.marginals.view(torch.int64), pi0.view(torch.int64),
+                               b.prob[:D].view(torch.int64)]).cpu().numpy()
+            f = lambda a: a.view(np.float64)
+            st = NashState(f(h[5 + 2 * n:]), None, f(h[5:5 + n]), float(f(h[0:1])[0]), int(h[1]), int(h[2]),
+                           float(f(h[3:4])[0]))
+            pi0, psum0 = f(h[5 + n:5 + 2 * n]), float(f(h[4:5])[0])
+        else:
+            st0 = ops.nash(t, n, 0, mult, self.S)
+            st = ops.nash(t, n, rounds, state=st0)
+            pi0, psum0 = st0.marginals, st0.psum
+        return PanelNash(t, st.prob, st.marginals, st.psum, pi0, psum0, st.ratio, st.rounds, st.best_row, n, ids)
+
     def __getstate__(self):
         f, m = self.multiplicities()
         rows = self._panel_rows(np.arange(self.distinct)) if self._panels is not None else None
@@ -1153,6 +1194,16 @@ class HostRowTables:
         """rows_maximin_host over the table's first ``length`` rows: ``(picks int64[rounds], MaximinState)``."""
         return rows_maximin_host(self._valid(table), n, rounds, shrink, resync, state)
 
+    def nash(self, table, n, rounds, mult=None, total=None, state=None):
+        """rows_nash_host over the table's first ``length`` rows: a NashState.  ``mult`` = one count per row of
+        the table (its first ``length`` are used) with their ``total``, or None for the uniform start."""
+        d = min(int(table.length[0]), table.cap)
+        return rows_nash_host(self._valid(table), n, rounds, None if mult is None else np.asarray(mult)[:d], total, state)
+
+    def marginals(self, table, n, prob):
+        """rows_marginals_host over the table's first ``length`` rows: ``(pi float64[n], psum)``."""
+        return rows_marginals_host(self._valid(table), np.asarray(prob)[:min(int(table.length[0]), table.cap)], n)
+
     def read(self, table, lists, draw_status=None):
         d = min(int(table.length[0]), table.cap)
         words = np.concatenate([np.zeros(4, np.uint32) if draw_status is None else np.asarray(draw_status, np.uint32),
@@ -1252,6 +1303,14 @@ class DeviceRowTables:
     def maximin(self, table, n, rounds, shrink=0.8, resync=16, state=None):
         """rows_maximin_device on this stream: ``(picks, MaximinBuffers)``, nothing waits."""
         return rows_maximin_device(table, n, rounds, shrink, resync, state, self.stream)
+
+    def nash(self, table, n, rounds, mult=None, total=None, state=None):
+        """rows_nash_device on this stream: a NashBuffers, nothing waits."""
+        return rows_nash_device(table, n, rounds, mult, total, state, self.stream)
+
+    def marginals(self, table, n, d_prob):
+        """rows_marginals_device on this stream: ``(pi, psum)`` as float64 tensors, nothing waits."""
+        return rows_marginals_device(table, n, d_prob, self.stream)
 
     def read(self, table, lists, draw_status=None):
         """The one host wait: [draw status | table status | length], then the D rows (and lists)."""
@@ -1770,6 +1829,279 @@ class PanelMaximin:
     def __repr__(self):
         return "PanelMaximin(%d panels, %d rounds, lower=%s, upper=%r)" % (len(self.panels), self.rounds, self.lower,
                                                                           self.upper)
+
+
+# --- the Nash-welfare lottery over a table (csrc/rows_nash.inc) -----------------------------------------------
+# The lottery over drawn panels with the greatest product (geometric mean) of selection probabilities, by Cover's
+# multiplicative iteration p_d <- p_d G_d / m, G_d = the sum of 1 / pi_i over row d, with the certificate
+# GM(pi / s) <= optimum <= GM(pi / s) * (max G / m) * s.  ``rows_marginals_host`` and ``rows_nash_host`` are the
+# contracts of csa_rows_marginals_async and csa_rows_nash_async in numpy, bit for bit.
+
+NASH_TILE = 1024
+
+NashState = namedtuple("NashState", "prob scores marginals ratio rounds best_row psum")
+NashState.__doc__ = """What csa_rows_nash_async keeps between calls, on the host: ``prob`` float64[D] (p),
+``scores`` float64[D] (G), ``marginals`` float64[n] (pi), and the state block's four words -- ``ratio`` (float:
+(max G / m) * psum), ``rounds`` done, ``best_row`` (the first row holding max G; PRICE_NONE for an empty table) and
+``psum`` (the ordered sum of p).  All belong to the same p."""
+
+NashBuffers = namedtuple("NashBuffers", "prob scores marginals block")
+NashBuffers.__doc__ = """The same state as device tensors: float64[cap], float64[cap], float64[n] and int64[4] (the
+state block: bits of ratio, rounds done, best row, bits of psum)."""
+
+
+def _nash_arguments(n, W, rounds):
+    n, rounds = int(n), int(rounds)
+    if not 0 < n <= 64 * W:
+        raise ValueError("n = %d agents do not fit rows of %d words" % (n, W))
+    if rounds < 0:
+        raise ValueError("rounds must not be negative")
+    return n, rounds
+
+
+def _tile_marginals(member, prob):
+    """member bool[D, n] (row-major), prob float64[D]: (pi, psum) in the marginal pass's order."""
+    D, n = member.shape
+    pi, psum = np.zeros(n, np.float64), np.float64(0.0)
+    with np.errstate(all="ignore"):
+        for t0 in range(0, D, NASH_TILE):
+            part, ps = np.zeros(n, np.float64), np.float64(0.0)
+            for d in range(t0, min(t0 + NASH_TILE, D)):
+                np.add(part, prob[d], out=part, where=member[d])      # part = np.where(bit, part + p[d], part)
+                ps = ps + prob[d]
+            pi = pi + part
+            psum = psum + ps
+    return pi, psum
+
+
+def rows_marginals_host(rows, prob, n):
+    """csa_rows_marginals_async's contract: ``(pi float64[n], psum)`` -- agent i's selection probability under the
+    lottery drawing row d with probability ``prob[d]``.  The rows are cut into tiles of 1024; within a tile every
+    agent's sum runs from +0.0 in ascending row order, one rounded add per row that holds the agent (a row that
+    does not adds nothing); the tiles' sums are added in ascending order from +0.0.  ``psum`` is the same
+    two-level sum over all rows."""
+    p = np.ascontiguousarray(rows, np.uint64)
+    if p.ndim != 2 or not 0 < int(n) <= 64 * p.shape[1]:
+        raise ValueError("rows must be uint64[D, W] with 0 < n <= 64 W")
+    q = np.ascontiguousarray(prob, np.float64).reshape(-1)
+    if len(q) != len(p):
+        raise ValueError("one probability per row")
+    pi, psum = _tile_marginals(np.ascontiguousarray(_member_columns(p, int(n)).T), q)
+    return pi, float(psum)
+
+
+def rows_nash_host(rows, n, rounds, mult=None, total=None, state=None):
+    """csa_rows_nash_async's contract: a NashState after ``rounds`` more rounds.  ``state=None`` starts
+    (CSA_NASH_START): ``p = mult / total`` (``mult`` one count per row, ``total`` defaulting to their sum; the
+    run's own lottery) or, without ``mult``, ``1 / D``; a NashState continues it (the input is left unchanged).
+    The pass: pi and psum as ``rows_marginals_host``; inv = 1 / pi for the m agents some row holds, +0.0
+    elsewhere; G = the rows' sums of inv in ascending agent index; the best row = the first holding max G; ratio
+    = (max G / m) * psum.  A round: p = p * (G / m), then the pass.  Every quotient is rounded before the product
+    it feeds.  An empty table: (no rows, pi = +0.0, ratio = +inf, 0 rounds, PRICE_NONE, psum = +0.0); rounds change
+    nothing.  Rows that hold nobody at all (m = 0) are outside the contract: the quotients by m give inf or NaN
+    here as on the device."""
+    p = np.ascontiguousarray(rows, np.uint64)
+    if p.ndim != 2:
+        raise ValueError("rows must be uint64[D, W]")
+    D, W = p.shape
+    n, rounds = _nash_arguments(n, W, rounds)
+    cols = _member_columns(p, n)
+    member = np.ascontiguousarray(cols.T)
+    held = cols.any(axis=1)
+    m = np.float64(int(held.sum()))
+
+    def the_pass(prob):
+        pi, psum = _tile_marginals(member, prob)
+        inv = np.where(held, np.float64(1.0) / pi, 0.0)
+        sc = _score_columns(cols, inv)
+        at, value = _best_of(sc)
+        return sc, pi, (np.float64(value) / m) * psum, at, psum
+
+    with np.errstate(all="ignore"):
+        if state is None:
+            if mult is not None:
+                mu = np.asarray(mult, np.int64).reshape(-1) & 0xFFFFFFFF
+                if len(mu) != D:
+                    raise ValueError("one multiplicity per row")
+                total = int(mu.sum()) if total is None else int(total)
+                if total <= 0:
+                    raise ValueError("multiplicities with a total of 0")
+                prob = mu.astype(np.float64) / np.float64(total)
+            else:
+                prob = np.full(D, np.float64(1.0) / np.float64(D) if D else 0.0, np.float64)
+            if not D:
+                return NashState(prob, np.zeros(0, np.float64), np.zeros(n, np.float64), float("inf"), 0, PRICE_NONE, 0.0)
+            sc, pi, ratio, at, psum = the_pass(prob)
+            done = 0
+        else:
+            prob, sc = np.array(state.prob, np.float64).reshape(-1), np.array(state.scores, np.float64).reshape(-1)
+            pi = np.array(state.marginals, np.float64).reshape(-1)
+            if len(prob) != D or len(sc) != D or len(pi) != n:
+                raise ValueError("the state is another table's")
+            ratio, done, at, psum = np.float64(state.ratio), int(state.rounds), int(state.best_row), np.float64(state.psum)
+        for _ in range(rounds if D else 0):
+            prob = prob * (sc / m)
+            sc, pi, ratio, at, psum = the_pass(prob)
+            done += 1
+    return NashState(prob, sc, pi, float(ratio), done, at, float(psum))
+
+
+def rows_marginals_device(table, n, d_prob, stream=None):
+    """Enqueue csa_rows_marginals_async over RowTable ``table`` with the float64 device tensor ``d_prob`` (one
+    entry per row of the table's capacity) on ``stream``; nothing waits.  Returns ``(pi, psum)``: float64[n] and
+    float64[1] on the device."""
+    import torch
+    L = N.lib()
+    dev = table.length.device
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(stream):
+        need = int(L.csa_rows_marginals_scratch_bytes(table.cap, table.W))
+        scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        pi = torch.empty(int(n), dtype=torch.float64, device=dev)
+        psum = torch.empty(1, dtype=torch.float64, device=dev)
+    N.check(L.csa_rows_marginals_async(N.ptr(table.rows), N.ptr(table.length), table.cap, table.W, int(n), N.ptr(d_prob),
+                                       N.ptr(pi), N.ptr(psum), N.ptr(scratch), need, ctypes.c_void_p(stream.cuda_stream)))
+    return pi, psum
+
+
+def rows_nash_device(table, n, rounds, mult=None, total=None, state=None, stream=None):
+    """Enqueue csa_rows_nash_async over RowTable ``table`` on ``stream`` (default: the current stream of the
+    table's device); nothing waits.  ``state=None`` starts on fresh buffers (CSA_NASH_START) from ``mult`` (a
+    device tensor of the table's uint32 multiplicity words, or host counts, which are uploaded) over ``total``, or
+    uniformly without ``mult``; a NashBuffers is continued in place.  Returns the NashBuffers.  Bad arguments raise
+    ValueError here or CsaError from the library, before any launch."""
+    import torch
+    L = N.lib()
+    dev = table.length.device
+    n, rounds = _nash_arguments(n, table.W, rounds)
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(stream):
+        need = int(L.csa_rows_nash_scratch_bytes(table.cap, table.W))
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        flags, d_mult = 0, None
+        if state is None:
+            flags = N.CSA_NASH_START
+            if mult is not None:
+                if total is None:
+                    raise ValueError("multiplicities on the device need their total")
+                if not _is_device_tensor(mult):
+                    mult = torch.from_numpy((np.asarray(mult, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).to(dev)
+                d_mult = mult if mult.dtype == torch.int32 else mult.to(torch.int32)
+                if d_mult.numel() < table.cap:
+                    raise ValueError("one multiplicity per row of the table")
+                if int(total) <= 0:
+                    raise ValueError("multiplicities with a total of 0")
+            state = NashBuffers(torch.empty(max(table.cap, 1), dtype=torch.float64, device=dev),
+                                torch.empty(max(table.cap, 1), dtype=torch.float64, device=dev),
+                                torch.empty(n, dtype=torch.float64, device=dev),
+                                torch.empty(4, dtype=torch.int64, device=dev))
+    N.check(L.csa_rows_nash_async(N.ptr(table.rows), N.ptr(table.length), table.cap, table.W, n, rounds, flags,
+                                  N.ptr(d_mult), int(total or 0), N.ptr(state.prob), N.ptr(state.scores),
+                                  N.ptr(state.marginals), N.ptr(state.block), N.ptr(scratch), need,
+                                  ctypes.c_void_p(stream.cuda_stream)))
+    return state
+
+
+def nash_buffers_host(buffers, length):
+    """A NashBuffers copied to the host as the NashState of a table of ``length`` rows (this waits)."""
+    d = int(length)
+    block = buffers.block.cpu().numpy().view(np.uint64)
+    return NashState(buffers.prob[:d].cpu().numpy(), buffers.scores[:d].cpu().numpy(), buffers.marginals.cpu().numpy(),
+                     float(block[0:1].view(np.float64)[0]), int(block[1]), int(block[2]),
+                     float(block[3:4].view(np.float64)[0]))
+
+
+def _geometric_mean(values):
+    import math
+    values = list(values)
+    if not values or min(values) <= 0.0:
+        return 0.0
+    return math.exp(math.fsum(math.log(v) for v in values) / len(values))
+
+
+class PanelNash:
+    """The Nash-welfare lottery over a run's distinct panels after ``rounds`` rounds of Cover's iteration.
+
+    ``probabilities``: float64[D], the lottery in the order of the run's sorted table (p / its sum).  ``alloc``:
+    agent id -> that lottery's selection probability of the agent (float; 0.0 for an agent no drawn panel holds).
+    ``covered_agents``: the agents some drawn panel holds; ``output_lines`` names the others.
+    ``geometric_mean``: ``exp(fsum(log alloc) / m)`` over the covered agents -- a lower bound on the greatest
+    geometric mean any lottery over the drawn panels reaches; ``gap``: the certificate (max G / m) * sum of p, at
+    least 1 up to rounding; ``upper = geometric_mean * gap`` bounds that optimum from above.
+    ``start_geometric_mean``: the same statistic at round 0 (LEGACY's own lottery over the drawn panels for
+    ``start="legacy"``).  ``best_row`` / ``best_panel``: the row the next round would raise most (None and an
+    empty set for an empty run).  An empty run: no probabilities, geometric means 0.0, gap and upper +inf."""
+
+    def __init__(self, table, prob, marginals, psum, start_marginals, start_psum, ratio, rounds, best_row, n, ids):
+        self._source, self._n, self._ids = table, int(n), list(ids)
+        ids = self._ids
+        prob = np.asarray(prob, np.float64)
+        with np.errstate(all="ignore"):
+            self.probabilities = prob / np.float64(psum) if len(prob) else prob.copy()
+            pi = np.asarray(marginals, np.float64) / np.float64(psum) if len(prob) else np.zeros(n)
+            pi0 = np.asarray(start_marginals, np.float64) / np.float64(start_psum) if len(prob) else np.zeros(n)
+        covered = np.asarray(start_marginals, np.float64) != 0.0      # every start has full support
+        self.alloc = {aid: float(pi[i]) for i, aid in enumerate(ids)}
+        self.covered_agents = frozenset(ids[i] for i in range(n) if covered[i])
+        self.geometric_mean = _geometric_mean(float(pi[i]) for i in range(n) if covered[i])
+        self.start_geometric_mean = _geometric_mean(float(pi0[i]) for i in range(n) if covered[i])
+        self.gap = float(ratio)
+        self.upper = self.geometric_mean * self.gap if len(prob) else float("inf")
+        self.rounds = int(rounds)
+        self.best_row = None if int(best_row) == PRICE_NONE else int(best_row)
+        self.best_panel = frozenset() if self.best_row is None else self._decode([self.best_row])[0]
+        self.output_lines = ["Agent %s not contained in any drawn panel." % (aid,) for i, aid in enumerate(ids)
+                             if not covered[i]]
+        if len(self.covered_agents) == len(ids):
+            self.output_lines.append("All agents are contained in some drawn panel.")
+
+    def _decode(self, index):
+        """The frozensets of the table's rows ``index``; only those rows are copied from a device table."""
+        from .instance import unpack_panel
+        t = self._source
+        if not len(index):
+            return []
+        if _is_device_tensor(t.rows):
+            import torch
+            at = torch.as_tensor(np.asarray(index, np.int64), device=t.rows.device)
+            words = t.rows.view(t.cap, t.W)[at].cpu().numpy()
+        else:
+            words = np.asarray(t.rows).view(np.int64).reshape(-1, t.W)[np.asarray(index, np.int64)]
+        return [frozenset(self._ids[q] for q in unpack_panel(np.ascontiguousarray(r).view(np.uint64), self._n))
+                for r in words]
+
+    def portfolio(self, threshold=1e-9):
+        """``(panels, probabilities)`` as ``portfolio_probabilities``, ``portfolio_composition`` and
+        ``legacy_portfolio_overlap`` take them: the rows with probability >= ``threshold`` in table order, their
+        probabilities divided by their ``fsum``.  Only the kept rows are decoded."""
+        import math
+        keep = np.flatnonzero(self.probabilities >= float(threshold))
+        kept = [float(x) for x in self.probabilities[keep]]
+        total = math.fsum(kept)
+        return self._decode(keep), [x / total for x in kept]
+
+    _FIELDS = ("alloc", "covered_agents", "geometric_mean", "start_geometric_mean", "gap", "upper", "rounds",
+               "best_row", "best_panel", "output_lines")
+
+    def __eq__(self, other):
+        return isinstance(other, PanelNash) and all(getattr(self, f) == getattr(other, f) for f in self._FIELDS) and \
+            np.array_equal(self.probabilities.view(np.uint64), other.probabilities.view(np.uint64))
+
+    __hash__ = None
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        t = self._source
+        if t is not None and _is_device_tensor(t.rows):       # pickles hold host arrays only
+            rows = t.rows.view(t.cap, t.W).cpu().numpy().view(np.uint64)
+            st["_source"] = RowTable(rows, None, None, np.array([t.cap], np.uint64), t.cap, t.W)
+        elif t is not None:
+            st["_source"] = RowTable(np.asarray(t.rows), None, None, np.asarray(t.length), t.cap, t.W)
+        return st
+
+    def __repr__(self):
+        return "PanelNash(%d panels, %d rounds, geometric_mean=%r, gap=%r)" % (len(self.probabilities), self.rounds,
+                                                                              self.geometric_mean, self.gap)
 
 
 PanelPrice = namedtuple("PanelPrice", "panel value row first multiplicity")

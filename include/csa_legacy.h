@@ -679,6 +679,69 @@ int csa_rows_maximin_async(const uint64_t *d_rows, const uint64_t *d_len, uint64
                            double *d_scores, uint32_t *d_cover, uint32_t *d_row_count, uint64_t *d_state,
                            uint32_t *d_picks /* or NULL */, void *d_scratch, uint64_t scratch_bytes, void *stream);
 
+/* The per-agent marginals of a weighted table: pi = M^T p, agent i's selection probability under the lottery
+ * that draws row d with probability d_prob[d].  Table, length and n as for csa_rows_price_async; a row past
+ * min(*d_len, cap) is never loaded and its d_prob entry never read.
+ * Summation-order contract (float64, no multiply, nothing to contract): the valid rows are cut into tiles of
+ * csa_rows_nash_tile() = 1024 consecutive rows.  For tile b and agent i, part[b][i] = the sum from +0.0, in
+ * ASCENDING row order, of d_prob[d] over the tile's valid rows that hold i: one rounded add per holder, a row
+ * that does not hold i adds nothing.  d_marginals[i] = the sum from +0.0 over ascending b of part[b][i], for
+ * i < n.  *d_psum = the same two-level sum over all valid rows.  A host loop gives the same bits
+ * (stats.rows_marginals_host).  An empty table writes +0.0 everywhere.
+ * d_scratch: csa_rows_marginals_scratch_bytes(cap, W) bytes, 8-byte aligned (the per-tile sums).  Two plain
+ * launches on the caller's stream, no host wait, no allocation.
+ * CSA_E_UNSUPPORTED for cap >= 2^32 - 1 or a W beyond the LDS of the pricing pass.  CSA_E_INVALID, before any
+ * device call, for what the pricing entry points refuse of the table and n, a NULL d_marginals or d_psum, a NULL
+ * d_prob with cap > 0, outputs that overlap each other, the inputs or the scratch, or a scratch that is NULL,
+ * short or misaligned when cap > 0. */
+uint32_t csa_rows_nash_tile(void);
+uint64_t csa_rows_marginals_scratch_bytes(uint64_t cap, int32_t W);
+int csa_rows_marginals_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                             const double *d_prob, double *d_marginals, double *d_psum, void *d_scratch,
+                             uint64_t scratch_bytes, void *stream);
+
+/* The Nash-welfare lottery over a sorted table of drawn panels: row probabilities p that maximise the product
+ * (the geometric mean) of the selection probabilities pi_i = the sum of p_d over the rows holding i, over the
+ * m agents some valid row holds.  Cover's multiplicative iteration: G_d = the sum of 1 / pi_i over the members
+ * of row d, p_d <- p_d * (G_d / m).  It keeps the sum of p at 1 in real arithmetic, raises the objective
+ * monotonically from a start with full support, and its fixed point is the optimum.  With s = the sum of p,
+ * ratio = (max_d G_d / m) * s bounds optimum / GM(pi / s) from above (Jensen), so after every round
+ * GM(pi / s) <= optimum <= GM(pi / s) * ratio, and ratio -> 1.
+ * State, all on the device, so that a call without CSA_NASH_START continues the previous one: d_prob
+ * (float64[cap], p), d_scores (float64[cap], G), d_marginals (float64[n], pi) and d_state (uint64[4] = bits of
+ * ratio, rounds done, the first row holding max G, bits of s) all belong to the same p after every round.
+ * Contract, every step float64 and rounded once (no fused multiply-add anywhere); D = min(*d_len, cap):
+ *   start (CSA_NASH_START): p[d] = (double)d_mult[d] / (double)total for d < D -- the run's own lottery when
+ *      total is its number of draws --, or 1.0 / (double)D with a NULL d_mult.  Then the pass below; rounds
+ *      done = 0.  Buffers need not be initialised.
+ *   pass: pi and s by csa_rows_marginals_async's contract over p; inv[i] = 1.0 / pi[i] where some valid row
+ *      holds i (m = how many do), else +0.0; G = csa_rows_price_async's scores under the weights inv (ascending
+ *      agent index from +0.0); the best row = the first holding the greatest G; ratio = (G_best / (double)m) * s,
+ *      the quotient rounded before the product.
+ *   round: p[d] = p[d] * (G[d] / (double)m) for d < D, the quotient rounded before the product; the pass; rounds
+ *      done += 1.
+ * m > 0 is assumed of a table that has valid rows: a drawn panel has k >= 1 members.  Valid rows that are all
+ * zero words give m = 0, and the quotients by m then put inf or NaN into p and the state; nothing refuses it, as
+ * the table is on the device.
+ * Nothing past D is read, scored or written in d_prob and d_scores.  An empty table: the start writes pi =
+ * +0.0 and the state (+inf, 0, CSA_PRICE_NONE, +0.0); rounds change nothing.  rounds == 0 with CSA_NASH_START
+ * only starts; without it nothing is launched.  Plain launches on the caller's stream (five a round), no
+ * host wait, no allocation; every call rebuilds the first holders, so the scratch need not survive between
+ * calls.  d_scratch: csa_rows_nash_scratch_bytes(cap, W) bytes, 8-byte aligned.
+ *
+ * CSA_E_UNSUPPORTED for cap >= 2^32 - 1 or a W beyond the LDS.  CSA_E_INVALID, before any device call, for
+ * what the pricing entry points refuse of the table and n, unknown flags, a NULL d_marginals / d_state, a NULL
+ * d_prob / d_scores with cap > 0, total == 0 with a non-NULL d_mult under CSA_NASH_START, state buffers that
+ * overlap each other, the table, the multiplicities, the length or the scratch, or a scratch that is NULL,
+ * short or misaligned. */
+#define CSA_NASH_START 0x1u
+uint64_t csa_rows_nash_scratch_bytes(uint64_t cap, int32_t W);
+int csa_rows_nash_async(const uint64_t *d_rows, const uint64_t *d_len, uint64_t cap, int32_t W, int32_t n,
+                        uint32_t rounds, uint32_t flags, const uint32_t *d_mult /* or NULL: uniform */,
+                        uint64_t total, double *d_prob /* [cap] */, double *d_scores /* [cap] */,
+                        double *d_marginals /* [n] */, uint64_t *d_state /* [4] */, void *d_scratch,
+                        uint64_t scratch_bytes, void *stream);
+
 /* Multi-GPU pair exchange: pack the upper triangle incl. the diagonal of the
  * n*n int64 pair counts row-major into n(n+1)/2 int32 (every count must be
  * < 2^31), and unpack it back (overwriting the upper triangle). */
